@@ -11,6 +11,11 @@ batch generation on the GPU, sparse Get (dedupe + all-to-all), deep-tower forwar
 sparse + dense Add, and the Clock (all-to-all of gradient rows + row-wise Adagrad on the
 owner shards, reduce-scatter + Adam + all-gather of the dense tower). Rank 0 prints one JSON
 line; `value` is the whole-job throughput and the time is the max over ranks.
+
+A plain run does only that: set up, warm up, time --steps steps, print the line. `--full` adds
+what else the benchmark measures by default (the per-collective `diag` steps of a run with several
+ranks); `--dump-outputs DIR` writes the state the last timed step left as DIR/*.npy, identical
+inputs from run to run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -33,6 +38,31 @@ import torch.distributed as dist  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 METRIC = "samples/sec (whole node) Criteo-shaped Wide&Deep BSP at 1/2/4/8 MI355X"
+DUMP_ROWS = 131072  # sparse rows sampled by --dump-outputs (x 36 floats: 19 MB of the 4.9 GB table)
+
+
+def dump_outputs(dirname, model, comm, loss):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the summed loss
+    the step returned and the parameter-server state it left (model drained). The batches and the
+    initial weights are seeded, so two builds run with the same arguments write comparable files.
+    Every rank calls this (the dense parameters are gathered); rank 0 writes."""
+    import numpy as np
+
+    dense = model.dense.full_master().float().cpu()
+    emb = model.emb
+    g = torch.Generator()
+    g.manual_seed(20240607)
+    n = emb.rows_local
+    idx = torch.randint(0, n, (DUMP_ROWS,), generator=g).sort().values if n > DUMP_ROWS else torch.arange(n)
+    idx = idx.to(emb.shard.device)
+    arrays = {"loss": loss.float().cpu(), "dense_params": dense, "sparse_rows": emb.shard[idx].float().cpu()}
+    for name, st in (("sparse_adagrad_state", emb.state), ("sparse_adagrad_state2", emb.state2)):
+        if st is not None:
+            arrays[name] = st[idx].float().cpu()
+    if comm.rank == 0 or comm.emulated:
+        os.makedirs(dirname, exist_ok=True)
+        for name, t in arrays.items():
+            np.save(os.path.join(dirname, name + ".npy"), t.numpy().astype(np.float32, copy=False))
 
 
 def main():
@@ -51,9 +81,17 @@ def main():
                          "reduce-scatter + all-gather after the backward)")
     ap.add_argument("--host-phases", type=int, default=0,
                     help="after the timed region: this many steps with per-phase host issue time (stderr)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed run, also everything else the benchmark measures by default: the 'diag' "
+                         "steps of a run with several ranks (--diag-steps). A plain run only sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float32): the loss it returned, the dense tower's parameters and a fixed, "
+                         "seeded sample of this rank's sparse rows with their Adagrad state")
     ap.add_argument("--diag-steps", type=int, default=None,
                     help="after the timed run: N more steps with per-collective timing and the host-sync audit, "
-                         "reported in the JSON line under 'diag' (default 10 with several ranks, else 0)")
+                         "reported in the JSON line under 'diag' (default 0; with --full 10 with several ranks)")
     ap.add_argument("--nccl-algo", default=None,
                     help="RCCL algorithm selection passed through as NCCL_ALGO (e.g. Ring, Tree; "
                          "tools/bench_kernels.py rccl measures the choices against the 7-link bound)")
@@ -140,10 +178,13 @@ def main():
     loss_last = float(l.item()) / args.batch
     samples = args.batch * (1 if emulated else n) * args.steps
     value = samples / elapsed
+    if args.dump_outputs:  # before any further step changes the tables
+        dump_outputs(args.dump_outputs, model, comm, l)
     # diagnostics AFTER the timed region (the timed steps ran without any of this): bytes and
     # achieved GB/s per collective kind, host issue time and host syncs per step -- so a multi-GPU
-    # run explains its own number (comm-bound vs host-bound vs compute-bound)
-    diag_steps = args.diag_steps if args.diag_steps is not None else (10 if n > 1 else 0)
+    # run explains its own number (comm-bound vs host-bound vs compute-bound). Only with --full
+    # (or an explicit --diag-steps): a plain run ends with its timed steps
+    diag_steps = args.diag_steps if args.diag_steps is not None else (10 if n > 1 and args.full else 0)
     diag = None
     if diag_steps > 0:
         from minips_amd.utils.syncaudit import SyncAudit

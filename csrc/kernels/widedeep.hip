@@ -448,8 +448,11 @@ namespace {
 // 128 (profiles/r4/ab_wd_knobs.txt); the two-level fold takes at most 256
 int head_grid(int64_t B) { return (int)std::max<int64_t>(1, std::min<int64_t>(256, (B + 63) / 64)); }
 
-// the partial slab + ticket of this device: allocated once (zero ticket), before any capture
-void head_ws(float** slab, unsigned** ticket) {
+// the partial slab + ticket of this device: allocated once (zero ticket), before any capture.
+// The zero fill is ordered on the caller's stream ``s``: a hipMemset runs on the null stream, which
+// a non-blocking compute stream does not wait for, so it could land on top of the partial rows the
+// first head was writing (a first-step loss and head gradient that missed some blocks' rows).
+void head_ws(float** slab, unsigned** ticket, hipStream_t s) {
   static thread_local std::vector<std::pair<int, void*>> ws_cache;
   int dev = 0;
   MINIPS_HIP_CHECK(hipGetDevice(&dev));
@@ -459,7 +462,7 @@ void head_ws(float** slab, unsigned** ticket) {
   const size_t slab_bytes = sizeof(float) * (256 + kHeadMaxGroups) * (2 * 512 + 2);
   if (!ws) {
     MINIPS_HIP_CHECK(hipMalloc(&ws, slab_bytes + 256));
-    MINIPS_HIP_CHECK(hipMemset(ws, 0, slab_bytes + 256));
+    MINIPS_HIP_CHECK(hipMemsetAsync(ws, 0, slab_bytes + 256, s));
     ws_cache.push_back({dev, ws});
   }
   *slab = static_cast<float*>(ws);
@@ -477,7 +480,7 @@ void wd_head(const bf16_t* H, int64_t B, int Hd, const bf16_t* w, const bf16_t* 
   const int grid = head_grid(B), defer = defer_fold ? 1 : 0;
   float* slab = nullptr;
   unsigned* ticket = nullptr;
-  head_ws(&slab, &ticket);
+  head_ws(&slab, &ticket, s);
   switch (Hd) {
     case 64 * 1: hipLaunchKernelGGL(wd_head_kernel<1>, grid, block, 0, s, H, B, Hd, w, b0, wide_logit, labels,
                                     dH, dw, db, dwide, loss_sum, dH_colsum, grad_scale, slab, ticket, defer); break;
@@ -498,7 +501,7 @@ void wd_head_fold(int64_t B, int Hd, float* dw, float* db, float* loss_sum, floa
     throw std::runtime_error("wd_head_fold: Hd must be 64, 128, 256 or 512, got " + std::to_string(Hd));
   float* slab = nullptr;
   unsigned* ticket = nullptr;
-  head_ws(&slab, &ticket);
+  head_ws(&slab, &ticket, s);
   const int NP = 2 * Hd + 2;
   hipLaunchKernelGGL(wd_head_fold_kernel, (NP + kFoldCols - 1) / kFoldCols, kFoldCols * kFoldChunks, 0, s, slab,
                      head_grid(B), Hd, dw, dH_colsum, db, loss_sum);

@@ -118,6 +118,46 @@ def test_bench_four_ranks_cpu():
     assert out["config"]["model"].startswith("PLUMBING TEST")
 
 
+def test_bench_plain_vs_full_and_dump_outputs_cpu(tmp_path):
+    """bench.py (CPU, small tables, one emulated rank of 2): a plain run stops after its timed
+    steps -- no 'diag' -- while --full runs and reports the per-collective diag steps; both write
+    the last timed step's outputs with --dump-outputs (float32 .npy, before any diag step), and
+    since the inputs are seeded the two runs' files are equal."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    from _util import ROOT
+
+    env = dict(os.environ, OMP_NUM_THREADS="1", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    outs = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
+               "--test-cards", ",".join(map(str, CARDS)), "--emulate-world", "2",
+               "--dump-outputs", str(tmp_path / name)] + extra
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        outs[name] = json.loads(lines[0])
+    for out in outs.values():
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "samples/s" and out["dtype"] == "bf16"
+        assert out["value"] == pytest.approx(64 * 1000.0 / out["ms_per_step"], rel=1e-3)
+    assert "diag" not in outs["plain"]
+    assert outs["full"]["diag"]["steps"] == 10 and outs["full"]["diag"]["collectives"]
+    names = sorted(p.name for p in (tmp_path / "plain").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "full").iterdir())
+    assert {"loss.npy", "dense_params.npy", "sparse_rows.npy"} <= set(names)
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+    loss = float(np.load(tmp_path / "plain" / "loss.npy")[0]) / 64
+    assert loss == pytest.approx(outs["plain"]["loss_last"], abs=1e-4)
+
+
 def _emulated_trace(world, consistency, staleness):
     from minips_amd.data.synthetic import CriteoSynth
     from minips_amd.models.feeder import LookaheadFeeder

@@ -222,3 +222,34 @@ def test_widedeep_one_rank_invariant_under_stream_delays(dev, monkeypatch, where
     got = run()
     for a, b in zip(ref, got):
         assert torch.equal(a, b), where
+
+
+def test_bench_outputs_identical_from_run_to_run(tmp_path):
+    """bench.py at its real configuration (Criteo cards, B = 16384, look-ahead feeder), twice, each
+    in a fresh process: the first step's loss and everything --dump-outputs writes (loss, dense
+    master, sampled sparse rows, Adagrad state) are bit-identical. A fresh process matters: the
+    head's partial-row workspace is allocated and zero-filled at the first head of a process, and
+    a fill not ordered before that head wiped part of its rows (a first-step loss of 0.07-0.28
+    instead of 0.692, and training that diverged from there). The first loss is also bounded from
+    below: the wide weights start at zero and the deep tower at small random weights, so the
+    logits are near 0 and the loss near ln 2 = 0.693; a fold that misses rows gives far less."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    firsts = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / name)], cwd=root, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        firsts.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["loss_first"])
+    assert firsts[0] == firsts[1] and 0.6 < firsts[0] < 0.8, firsts
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert len(names) == 5, names
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n

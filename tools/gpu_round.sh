@@ -107,8 +107,9 @@ if [[ $STAGE == emu ]]; then
   timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 10 ${BENCH_ARGS} > gpurun_out/emu_w1.log 2>&1 || { tail -30 gpurun_out/emu_w1.log; exit 1; }
   grep "^{" gpurun_out/emu_w1.log | cut -c1-200
   for w in ${EMU_WORLDS:-2 8}; do
-    timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 10 --emulate-world $w ${BENCH_ARGS} > gpurun_out/emu_w$w.log 2>&1 || { tail -30 gpurun_out/emu_w$w.log; exit 1; }
-    grep "^{" gpurun_out/emu_w$w.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('emulated', $w, d['ms_per_step'], 'ms/step', json.dumps(d.get('diag')))"
+    log=$(mktemp)  # (--full: the emulated ranks' per-collective diag, printed below)
+    timeout -k 10 300 python bench.py --steps ${STEPS:-100} --warmup 10 --emulate-world $w --full ${BENCH_ARGS} > $log 2>&1 || { tail -30 $log; exit 1; }
+    grep "^{" $log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('emulated', $w, d['ms_per_step'], 'ms/step', json.dumps(d.get('diag')))"
   done
   prof_env
   w=${EMU_PROF:-8}
