@@ -5,6 +5,8 @@
 * ``_kernels``  -- the gfx950 HIP kernels (torch extension). Required whenever a GPU tensor
   reaches an op: on a GPU box a missing or stale build raises instead of silently falling
   back to eager PyTorch.
+* ``_evalk``    -- the held-out evaluation kernels (binned-AUC histograms, fused eval head): a second,
+  small torch extension with the same rule -- a GPU tensor without it raises.
 """
 from __future__ import annotations
 
@@ -13,6 +15,8 @@ import os
 
 _kernels = None
 _kernels_err: Exception | None = None
+_evalk = None
+_evalk_err: Exception | None = None
 _runtime = None
 _runtime_err: Exception | None = None
 
@@ -35,6 +39,24 @@ def kernels():
     return _kernels
 
 
+def evalk():
+    """Return the HIP evaluation-kernel module or raise a loud error."""
+    global _evalk, _evalk_err
+    if _evalk is None and _evalk_err is None:
+        try:
+            import torch  # noqa: F401  (libtorch must be loaded first)
+
+            _evalk = importlib.import_module("minips_amd._evalk")
+        except Exception as e:  # pragma: no cover - depends on the build
+            _evalk_err = e
+    if _evalk is None:
+        raise RuntimeError(
+            "minips_amd._evalk (gfx950 HIP evaluation kernels) is not built or failed to load: "
+            f"{_evalk_err!r}. Run `python tools/build.py` (or __graft_entry__.build())."
+        )
+    return _evalk
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     global _runtime, _runtime_err
@@ -53,6 +75,14 @@ def runtime():
 def kernels_available() -> bool:
     try:
         kernels()
+        return True
+    except RuntimeError:
+        return False
+
+
+def evalk_available() -> bool:
+    try:
+        evalk()
         return True
     except RuntimeError:
         return False

@@ -40,6 +40,15 @@ class CriteoSynth:
         self.hot_alpha = hot_alpha
         self.w_dense = torch.randn(n_dense, generator=self.gen, device=self.device) / math.sqrt(n_dense)
 
+    def holdout(self, seed: int) -> "CriteoSynth":
+        """A held-out stream of the SAME labelling function: the teacher (``w_dense``, the cards) is
+        this generator's, the samples are an independent stream drawn from ``seed`` (a generator
+        merely constructed with another seed would draw another teacher)."""
+        g = CriteoSynth(self.batch, cards=self.cards, n_dense=self.n_dense, device=self.device, seed=seed,
+                        hot_alpha=self.hot_alpha)
+        g.w_dense = self.w_dense.clone()
+        return g
+
     def next(self):
         B, F = self.batch, self.F
         if self.device.type == "cuda":
@@ -118,6 +127,11 @@ class DLRMSynth:
         self._step = 0
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
+
+    def holdout(self, seed: int) -> "DLRMSynth":
+        """A held-out stream: the labels are a fixed function of the features (no teacher state), so a
+        fresh seed is an independent sample of the same task."""
+        return DLRMSynth(self.batch, self.F, self.num_rows, self.n_dense, device=self.device, seed=seed)
 
     def next(self):
         B = self.batch

@@ -116,6 +116,61 @@ class DLRM(LookaheadPlans):
             )
         return self._bufs[B]
 
+    def _forward(self, b, P, dense):
+        """Bottom MLP -> dot interaction -> top MLP over the buffers ``b`` (V's embedding part is
+        already looked up); leaves the last hidden layer in b["H"]."""
+        cfg = self.cfg
+        F, D = cfg.F, cfg.D
+        ba = b["bacts"]
+        ba[0][:, : cfg.n_dense].copy_(dense)
+        for i, l in enumerate(self.bottom):
+            out = ba[i + 1] if i + 1 < len(self.bottom) else b["V"][:, F * D:]
+            l.forward(P, ba[i], out, "relu")
+        ta = b["tacts"]
+        ops.dlrm_interact_fwd(b["V"], self.NV, D, ta[0], dense_idx=F)
+        for i, l in enumerate(self.top):
+            out = ta[i + 1] if i + 1 < len(self.top) else b["H"]
+            l.forward(P, ta[i], out, "relu")
+
+    def _eval_buffers(self, B):
+        """The forward's buffers for evaluate(): its own (the training step's stay untouched)."""
+        bufs = self.__dict__.setdefault("_ebufs", {})
+        if B not in bufs:
+            dev, cfg = self.comm.device, self.cfg
+            bf = dict(dtype=torch.bfloat16, device=dev)
+            bufs[B] = dict(
+                bacts=[ext_activation(B, d, dev) for d in [cfg.n_dense, *cfg.bottom]],
+                V=torch.zeros(B, self.NV * cfg.D, **bf),
+                tacts=[ext_activation(B, self.n_int, dev)] + [ext_activation(B, d, dev) for d in cfg.top[:-1]],
+                H=torch.empty(B, cfg.top[-1], **bf),
+            )
+        return bufs[B]
+
+    def evaluate(self, batches, evaluator=None) -> dict:
+        """Held-out evaluation: ``batches`` yields (dense, keys, labels); every rank calls it with the
+        same number of batches (the key plans and the final reduce are collective). Forward only --
+        plan, Get, lookup, bottom MLP, interaction, top MLP, ops.eval_head -- with no Add, no Clock
+        and no write to a gradient buffer, the loss accumulator or a pending look-ahead plan.
+        Returns BinaryEvaluator.result() of all ranks' samples."""
+        from ..utils.evalmetrics import BinaryEvaluator
+
+        cfg = self.cfg
+        if cfg.transport == "onesided":
+            raise NotImplementedError("DLRM.evaluate: the onesided transport is not supported (its Gets move the "
+                                      "SSP gate's staleness statistics and need a clock); evaluate on 'collective'")
+        ev = evaluator if evaluator is not None else BinaryEvaluator(self.comm.device)
+        F, D, h = cfg.F, cfg.D, cfg.top[-1]
+        P = self.dense.get()
+        hw = self.layout.view(P, "head")
+        for dense, keys, labels in batches:
+            b = self._eval_buffers(dense.shape[0])
+            rows, plan = self.emb.get(keys, plan=self.emb.plan(keys))  # (not _take_plan: look-ahead plans survive)
+            ops.lookup_rows(rows, plan.inv, F, D, b["V"])
+            self._forward(b, P, dense)
+            ev.update_head(b["H"], hw[:h], hw[h:h + 1], None, labels)
+        ev.reduce(self.comm)
+        return ev.result()
+
     def train_step(self, dense, keys, labels, next_keys=None, next_on_plan_stream: bool = False):
         cfg = self.cfg
         B, F, D = dense.shape[0], cfg.F, cfg.D
@@ -129,16 +184,8 @@ class DLRM(LookaheadPlans):
         # V = [emb_0 .. emb_{F-1} | bottom(dense)]  (the dense vector is the last one)
         ops.lookup_rows(rows, plan.inv, F, D, b["V"])
         P = self.dense.get()
-        ba = b["bacts"]
-        ba[0][:, : cfg.n_dense].copy_(dense)
-        for i, l in enumerate(self.bottom):
-            out = ba[i + 1] if i + 1 < len(self.bottom) else b["V"][:, F * D:]
-            l.forward(P, ba[i], out, "relu")
-        ta = b["tacts"]
-        ops.dlrm_interact_fwd(b["V"], self.NV, D, ta[0], dense_idx=F)
-        for i, l in enumerate(self.top):
-            out = ta[i + 1] if i + 1 < len(self.top) else b["H"]
-            l.forward(P, ta[i], out, "relu")
+        ba, ta = b["bacts"], b["tacts"]
+        self._forward(b, P, dense)
         hw = self.layout.view(P, "head")
         hg = self.layout.view(G, "head")
         h = cfg.top[-1]

@@ -283,6 +283,50 @@ class WideDeep(LookaheadPlans):
         w4 = self.view(P, "w4").float()
         return b["H3"].float() @ w4[:h] + w4[h] + b["wide"]
 
+    def _eval_buffers(self, B):
+        """Activation buffers of evaluate(): its own, so an evaluation between two training steps
+        leaves the step's buffers (still read by the side stream's weight gradients) alone."""
+        bufs = self.__dict__.setdefault("_ebufs", {})
+        if B not in bufs:
+            dev, cfg = self.comm.device, self.cfg
+            bf = dict(dtype=torch.bfloat16, device=dev)
+            X = torch.zeros(B, self.k_pad[0], **bf)
+            X[:, self.k_in[0]] = 1.0
+            bufs[B] = dict(X=X, wide=torch.empty(B, dtype=torch.float32, device=dev),
+                           **{f"H{i + 1}": torch.empty(B, n, **bf) for i, n in enumerate(cfg.hidden)})
+        return bufs[B]
+
+    def evaluate(self, batches, evaluator=None) -> dict:
+        """Held-out evaluation: ``batches`` yields (dense, keys, labels); every rank calls it with the
+        same number of batches (the key plans and the final reduce are collective). Forward only --
+        plan, Get, assemble, the three forward GEMMs, ops.eval_head -- with no Add, no Clock and no
+        write to a gradient buffer, the loss accumulator, a launch-list recording or a pending
+        look-ahead plan: training continues afterwards exactly as without it. Returns
+        BinaryEvaluator.result() of all ranks' samples (``evaluator``: accumulate into this one)."""
+        from ..utils.evalmetrics import BinaryEvaluator
+
+        cfg = self.cfg
+        if "onesided" in (cfg.transport, cfg.dense_transport):
+            raise NotImplementedError("WideDeep.evaluate: the onesided transport is not supported (its Gets move the "
+                                      "SSP gate's staleness statistics and need a clock); evaluate on 'collective'")
+        ev = evaluator if evaluator is not None else BinaryEvaluator(self.comm.device)
+        F, D, h = cfg.F, cfg.emb_dim, cfg.hidden[-1]
+        # the last train step's Adam (side stream) before W is read, as forward() does -- but the
+        # pending events stay for the next train step, whose own waits then find what they expect
+        pend_side = self.__dict__.get("_side_pending")
+        if pend_side is not None:
+            streams.current(self.comm.device).wait_event(pend_side[1])
+        P = self.dense.get()
+        w4 = self.view(P, "w4")
+        for dense, keys, labels in batches:
+            b = self._eval_buffers(dense.shape[0])
+            rows, plan = self.emb.get(keys, plan=self.emb.plan(keys))  # (not _take_plan: look-ahead plans survive)
+            ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
+            self._forward(b, P)
+            ev.update_head(b["H3"], w4[:h], w4[h:h + 1], b["wide"], labels)
+        ev.reduce(self.comm)
+        return ev.result()
+
     @traced("wd.train_step")
     def train_step(self, dense, keys, labels, next_keys=None, next_on_plan_stream: bool = False) -> torch.Tensor:
         """One BSP superstep: Get, forward, backward, Add, Clock. Returns the summed loss

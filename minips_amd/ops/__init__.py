@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from .._native import kernels
+from .._native import evalk, kernels
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -600,6 +600,57 @@ def wd_head_fold(B, Hd, dw, db, loss_sum, dH_colsum=None):
     stream (recordable into a LaunchList). No-op on the CPU (wd_head added them)."""
     if _gpu(dw):
         (kernels() if _REC is None else _REC.lst).wd_head_fold(int(B), int(Hd), dw, db, loss_sum, dH_colsum)
+
+
+# ----------------------------------------------------------------------------- held-out evaluation
+EVAL_LOSS_SCALE = float(1 << 24)  # loss_fx counts units of 2^-24
+
+
+def _eval_bins(acc) -> int:
+    NB = (acc.numel() - 2) // 2
+    if acc.dtype != torch.int64 or acc.numel() != 2 * NB + 2 or not 32 <= NB <= 8192 or NB & (NB - 1):
+        raise RuntimeError(f"acc must be int64 [2*NB + 2] with NB a power of two in [32, 8192], got "
+                           f"{acc.dtype} [{acc.numel()}]")
+    return NB
+
+
+def binary_hist(logits, labels, acc):
+    """Accumulate fp32 ``logits`` [n] with 0/1 float ``labels`` into ``acc`` (int64, neg[NB] | pos[NB] |
+    loss_fx | n_nan). Per sample: a NaN logit only counts in n_nan; y = label > 0.5;
+    bin = min(NB-1, floor((clamp(z, -16, 16) + 16) * (NB/32))) (the logit is binned, not the probability:
+    no transcendental, so CPU and GPU bins agree bit for bit); loss_fx += round(l * 2^24) with
+    l = max(zl,0) - zl*y + log1p(exp(-|zl|)), zl = clamp(z, -64, 64). Integer sums: independent of order."""
+    NB = _eval_bins(acc)
+    if _gpu(logits):
+        evalk().binary_hist(logits, labels, acc)
+        return
+    z = logits.reshape(-1).to(torch.float32)
+    y = labels.reshape(-1).to(torch.float32) > 0.5
+    ok = ~torch.isnan(z)
+    acc[2 * NB + 1] += int((~ok).sum())
+    z, y = z[ok], y[ok]
+    zc = torch.clamp(z, -16.0, 16.0)
+    bins = torch.clamp_max(torch.floor((zc + 16.0) * float(NB // 32)).to(torch.int64), NB - 1)
+    acc[:NB] += torch.bincount(bins[~y], minlength=NB)
+    acc[NB:2 * NB] += torch.bincount(bins[y], minlength=NB)
+    zl = torch.clamp(z, -64.0, 64.0)
+    l = torch.clamp_min(zl, 0) - zl * y.to(torch.float32) + torch.log1p(torch.exp(-zl.abs()))
+    acc[2 * NB] += torch.round(l * EVAL_LOSS_SCALE).to(torch.int64).sum()
+
+
+def eval_head(H, w, b0, wide, labels, acc, logits_out=None):
+    """The forward half of wd_head fused with binary_hist: z = H . w + b0 + wide (fp32 accumulate; ``wide``
+    may be None) goes through binary_hist's rule into ``acc``; ``logits_out`` (fp32 [B], optional)
+    receives z. H: bf16 [B, Hd] rows (a column-sliced view is fine), Hd % 8 == 0, 8 <= Hd <= 1024."""
+    if _gpu(H):
+        evalk().eval_head_hist(H, w, b0, wide, labels, acc, logits_out)
+        return
+    z = H.float() @ w.float() + b0.float()
+    if wide is not None:
+        z = z + wide
+    if logits_out is not None:
+        logits_out.copy_(z)
+    binary_hist(z, labels, acc)
 
 
 def emb_csr_positions(members):

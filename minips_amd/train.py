@@ -6,7 +6,8 @@
 Flags keep the reference names where the reference has them (lr_example.cpp:20-56, §5.6):
 checkpoint_toggle, checkpoint_file_prefix, use_weight_file, heartbeat_interval, report_prefix,
 report_interval, with_injected_straggler, kModelType (= --consistency), kStaleness, batch_size,
-num_iters (= --steps), alpha (LR). Extra: --fail_rank/--fail_step fault injection, --metrics_dir.
+num_iters (= --steps), alpha (LR). Extra: --fail_rank/--fail_step fault injection, --metrics_dir,
+--eval_every/--eval_batches/--eval_seed (held-out AUC and log loss of widedeep / dlrm; off by default).
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -96,10 +97,23 @@ def parse(argv=None):
     ap.add_argument("--assigner_master_port", type=int, default=0,
                     help="> 0: rank 0 serves locality-aware block assignment (HDFSBlockAssigner) on this port")
     ap.add_argument("--num_dims", type=int, default=0, help="feature count (reference flag; 0: infer / default)")
+    ap.add_argument("--eval_every", type=int, default=0,
+                    help="> 0: every N steps and at the end, all ranks evaluate --eval_batches held-out batches "
+                         "(widedeep / dlrm: exact binned AUC and log loss); 0: off, nothing changes")
+    ap.add_argument("--eval_batches", type=int, default=4, help="held-out batches per rank and evaluation")
+    ap.add_argument("--eval_seed", type=int, default=12345,
+                    help="seed of the held-out stream (re-created at every evaluation: the same batches each time)")
     args = ap.parse_args(argv)
+    if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
+        ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
+    if args.eval_every > 0 and args.model not in ("widedeep", "dlrm"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep and dlrm, not {args.model}")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
         args.transport = ("onesided" if args.model in ("dlrm", "widedeep") and args.consistency in ("ssp", "asp")
                           else "collective")
+    if args.eval_every > 0 and args.transport == "onesided":
+        ap.error("--eval_every: held-out evaluation needs --transport collective (evaluate() is not implemented "
+                 "on the onesided transport)")
     return args
 
 
@@ -289,6 +303,9 @@ class _Skippable:
         for _ in range(n):
             self.inner.next()
 
+    def holdout(self, seed):
+        return self.inner.holdout(seed)
+
 
 class _Batches:
     def __init__(self, shard, B, seed):
@@ -306,6 +323,9 @@ class _DLRMData:
 
     def next(self):
         return self.gen.next()
+
+    def holdout(self, seed):
+        return self.gen.holdout(seed)
 
 
 class _GaussData:
@@ -461,6 +481,29 @@ def main(argv=None):
                         mode=args.fail_mode, heartbeat=hb)
     log = metrics.get_logger()
     losses = []
+    evals = []  # [iteration, auc, logloss, n] per held-out evaluation (--eval_every)
+    t_eval = 0.0  # wall time spent evaluating since t_steady (excluded from steady_ms_per_iter)
+
+    def evaluate(it_done: int):
+        """All ranks: the same --eval_batches held-out batches every time (the stream is re-created:
+        this rank's teacher, its own slice by seed), summed over the ranks."""
+        nonlocal t_eval
+        if comm.device.type == "cuda":
+            torch.cuda.synchronize(comm.device)
+        t0 = time.perf_counter()
+        held = make_data().holdout(args.eval_seed * 1000 + rank)
+        r = model.evaluate(held.next() for _ in range(args.eval_batches))
+        if comm.device.type == "cuda":
+            torch.cuda.synchronize(comm.device)
+        dt = time.perf_counter() - t0
+        t_eval += dt
+        evals.append([it_done, r["auc"], r["logloss"], r["n"]])
+        log.event("eval", step=it_done, auc=r["auc"], auc_slack=r["auc_slack"], logloss=r["logloss"], n=r["n"],
+                  n_pos=r["n_pos"], n_nan=r["n_nan"], eval_ms=round(dt * 1e3, 3))
+        if rank == 0:
+            auc = "nan" if r["auc"] is None else f"{r['auc']:.5f}"
+            ll = "nan" if r["logloss"] is None else f"{r['logloss']:.5f}"
+            print(f"Eval iteration={it_done} auc={auc} logloss={ll} n={r['n']}", flush=True)
     report = open(args.report_prefix + f"report_{rank}", "a") if args.report_prefix else None
     t_start = time.perf_counter()
     t_steady, n_steady = None, 0
@@ -494,6 +537,7 @@ def main(argv=None):
         data = make_data()
         data.skip(it0)
         losses = [x for x in losses if x[0] < it0]
+        evals[:] = [e for e in evals if e[0] <= it0]
         metrics.fault_tolerance_phase(5, f"rank {rank} rolled back in place to iteration {it0} "
                                          f"(failed rank {d.get('failed_rank')}, generation {generation})")
         hb.state = "run"
@@ -539,6 +583,7 @@ def main(argv=None):
         data = make_data()
         data.skip(it0)
         losses = [x for x in losses if x[0] < it0]
+        evals[:] = [e for e in evals if e[0] <= it0]
         metrics.fault_tolerance_phase(5, f"rank {rank} rescaled in place to {world} ranks at iteration {it0} "
                                          f"(generation {generation})")
         hb.state = "run"
@@ -565,7 +610,7 @@ def main(argv=None):
             if it == start + args.timing_skip and t_steady is None:
                 if comm.device.type == "cuda":
                     torch.cuda.synchronize(comm.device)
-                t_steady, n_steady = time.perf_counter(), args.steps - it
+                t_steady, n_steady, t_eval = time.perf_counter(), args.steps - it, 0.0
             with _ckpt_state(hb):  # checkpoint phases are not steps: their own heartbeat state
                 if args.checkpoint_commit == "async":
                     ck.try_commit()  # publishes an in-flight checkpoint once every rank's files are written
@@ -594,6 +639,8 @@ def main(argv=None):
             if hb:
                 hb.progress(it)
             it += 1
+            if args.eval_every > 0 and it % args.eval_every == 0 and it < args.steps:
+                evaluate(it)
         except Exception as e:  # noqa: BLE001
             if not (inplace and hb is not None and comm.world > 1 and _is_comm_failure(e)):
                 raise
@@ -604,7 +651,10 @@ def main(argv=None):
     model.drain()
     if comm.device.type == "cuda":
         torch.cuda.synchronize(comm.device)
-    steady_ms = (time.perf_counter() - t_steady) * 1e3 / n_steady if t_steady is not None and n_steady else None
+    steady_ms = ((time.perf_counter() - t_steady - t_eval) * 1e3 / n_steady
+                 if t_steady is not None and n_steady else None)
+    if args.eval_every > 0:
+        evaluate(args.steps)
     with _ckpt_state(hb):
         ck.commit()
     # parameter checksum over every table (identical on all ranks): the parameter values only
@@ -627,7 +677,8 @@ def main(argv=None):
                               checksum=[round(float(x), 6) for x in sums.cpu()],
                               total_ms=round((time.perf_counter() - t_start) * 1e3, 1),
                               steady_ms_per_iter=round(steady_ms, 4) if steady_ms is not None else None,
-                              world=comm.world, generation=generation)),
+                              world=comm.world, generation=generation,
+                              **({"evals": evals} if args.eval_every > 0 else {}))),
               flush=True)
     if comm.world > 1:
         comm.barrier()

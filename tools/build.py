@@ -9,6 +9,8 @@ Targets
   kernels   csrc/kernels/*.hip           -> build/obj/k_*.o   (hipcc --offload-arch=gfx950)
   comm      csrc/comm/*.cc               -> build/obj/c_*.o   (native RCCL data plane, linked into ops_py)
   ops_py    csrc/bindings/ops_py.cpp     -> minips_amd/_kernels*.so   (hipcc, torch headers)
+  eval_py   csrc/bindings/eval_py.cpp    -> minips_amd/_evalk*.so     (the held-out evaluation ops: a second,
+            small torch extension that links k_evalmetrics.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -88,7 +90,7 @@ def _compile_many(jobs: list[tuple[str, list[str], list[str]]]) -> None:
             f.result()
 
 
-def _torch_flags() -> tuple[list[str], list[str]]:
+def _torch_flags(name: str = "_kernels") -> tuple[list[str], list[str]]:
     import torch.utils.cpp_extension as ce  # noqa: WPS433
 
     inc = []
@@ -98,7 +100,7 @@ def _torch_flags() -> tuple[list[str], list[str]]:
     new_api = "device_type" in ce.library_paths.__code__.co_varnames
     libdir = ce.library_paths("cuda")[0] if new_api else ce.library_paths(True)[0]
     py_inc = sysconfig.get_paths()["include"]
-    cflags = inc + ["-I", py_inc, "-DTORCH_EXTENSION_NAME=_kernels", "-DTORCH_API_INCLUDE_EXTENSION_H",
+    cflags = inc + ["-I", py_inc, f"-DTORCH_EXTENSION_NAME={name}", "-DTORCH_API_INCLUDE_EXTENSION_H",
                     "-D_GLIBCXX_USE_CXX11_ABI=1", "-DUSE_ROCM=1", "-D__HIP_PLATFORM_AMD__=1"]
     ldflags = ["-L", libdir, "-Wl,-rpath," + libdir, "-lc10", "-ltorch", "-ltorch_cpu", "-ltorch_python",
                "-lc10_hip", "-ltorch_hip"]
@@ -197,6 +199,21 @@ def build_ops_py(kobjs: list[str], robjs: list[str] = ()) -> str:
     return out
 
 
+def build_eval_py(kobjs: list[str]) -> str:
+    """minips_amd/_evalk: the evaluation bindings over k_evalmetrics.o alone."""
+    src = os.path.join(ROOT, "csrc/bindings/eval_py.cpp")
+    out = os.path.join(PKG, "_evalk" + EXT)
+    bobj = os.path.join(OBJ, "eval_py.o")
+    cflags, ldflags = _torch_flags("_evalk")
+    kobjs = [o for o in kobjs if os.path.basename(o) == "k_evalmetrics.o"]
+    hdrs = _headers("csrc/kernels", "csrc/bindings")
+    _compile_many([(bobj, [src] + hdrs, [HIPCC, "-O2", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}",
+                                         *cflags, "-c", src, "-o", bobj])])
+    _compile_many([(out, [bobj] + kobjs,
+                    [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", bobj, *kobjs, "-o", out, *ldflags])])
+    return out
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -223,7 +240,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 
 def main(argv: list[str]) -> int:
-    targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py"}
+    targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -239,9 +256,13 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py"}:
-        kobjs = kernel_objs() + comm_objs()
-        print("built", build_ops_py(kobjs, objs))  # always relink: a stale .so would silently run old kernels
+    if targets & {"kernels", "ops_py", "eval_py"}:
+        kobjs = kernel_objs()
+        if targets & {"kernels", "ops_py"}:
+            # always relink: a stale .so would silently run old kernels
+            print("built", build_ops_py(kobjs + comm_objs(), objs))
+        if targets & {"kernels", "eval_py"}:
+            print("built", build_eval_py(kobjs))
     return 0
 
 
