@@ -7,6 +7,8 @@
   back to eager PyTorch.
 * ``_evalk``    -- the held-out evaluation kernels (binned-AUC histograms, fused eval head): a second,
   small torch extension with the same rule -- a GPU tensor without it raises.
+* ``_optk``     -- the global-norm gradient-clipping kernels of the dense clock (fp64 partial sums of
+  squares, the clipping Adam): a third small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -17,6 +19,8 @@ _kernels = None
 _kernels_err: Exception | None = None
 _evalk = None
 _evalk_err: Exception | None = None
+_optk = None
+_optk_err: Exception | None = None
 _runtime = None
 _runtime_err: Exception | None = None
 
@@ -57,6 +61,24 @@ def evalk():
     return _evalk
 
 
+def optk():
+    """Return the HIP gradient-clipping kernel module or raise a loud error."""
+    global _optk, _optk_err
+    if _optk is None and _optk_err is None:
+        try:
+            import torch  # noqa: F401  (libtorch must be loaded first)
+
+            _optk = importlib.import_module("minips_amd._optk")
+        except Exception as e:  # pragma: no cover - depends on the build
+            _optk_err = e
+    if _optk is None:
+        raise RuntimeError(
+            "minips_amd._optk (gfx950 HIP gradient-clipping kernels) is not built or failed to load: "
+            f"{_optk_err!r}. Run `python tools/build.py` (or __graft_entry__.build())."
+        )
+    return _optk
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     global _runtime, _runtime_err
@@ -83,6 +105,14 @@ def kernels_available() -> bool:
 def evalk_available() -> bool:
     try:
         evalk()
+        return True
+    except RuntimeError:
+        return False
+
+
+def optk_available() -> bool:
+    try:
+        optk()
         return True
     except RuntimeError:
         return False

@@ -29,7 +29,7 @@ import torch
 
 from .. import ops
 from ..ps.comm import Comm
-from ..ps.tables import DenseTable
+from ..ps.tables import DenseTable, lr_schedule_from
 from .layers import SideStream, Linear, ParamLayout, align, ext_activation
 
 
@@ -52,6 +52,12 @@ class GPT2Config:
     # soon as its backward finished, overlapping the rest of the backward (DenseTable overlap_w1;
     # GPT2_OVERLAP_W1 off: one Adam over the whole table after the backward)
     overlap_w1: bool = True
+    # global-norm gradient clipping (None: off) and the warmup + cosine lr schedule (0 / 0: constant lr) of
+    # the table (DenseTable clip_norm / LRSchedule)
+    clip_norm: float | None = None
+    lr_warmup: int = 0
+    lr_decay_steps: int = 0
+    lr_min_ratio: float = 0.0
 
     @property
     def vocab_pad(self):
@@ -102,7 +108,8 @@ class GPT2:
         starts = [L.entries[f"h{i}.ln1_g"][0] for i in range(cfg.n_layer)] if cfg.bucketed else None
         self.table = DenseTable(comm, L.size, optimizer="adam", lr=cfg.lr, consistency=cfg.consistency,
                                 staleness=cfg.staleness, weight_decay=cfg.weight_decay, betas=(0.9, 0.95),
-                                buckets=starts, overlap_w1=cfg.overlap_w1)
+                                buckets=starts, overlap_w1=cfg.overlap_w1, clip_norm=cfg.clip_norm,
+                                lr_schedule=lr_schedule_from(cfg.lr_warmup, cfg.lr_decay_steps, cfg.lr_min_ratio))
         self._layer_bucket = [self.table.bucket_for_layer(x) for x in starts] if starts else None
         g = torch.Generator().manual_seed(cfg.seed)
         full = torch.zeros(L.size)

@@ -10,7 +10,7 @@ import torch
 
 from .. import ops
 from ..ps.comm import Comm
-from ..ps.tables import DenseTable
+from ..ps.tables import DenseTable, lr_schedule_from
 from .layers import Linear, ParamLayout, SideStream, align, ext_activation
 
 
@@ -24,6 +24,12 @@ class MLPConfig:
     consistency: str = "bsp"
     staleness: int = 0
     seed: int = 0
+    # global-norm gradient clipping (None: off) and the warmup + cosine lr schedule (0 / 0: constant lr) of
+    # the table (DenseTable clip_norm / LRSchedule)
+    clip_norm: float | None = None
+    lr_warmup: int = 0
+    lr_decay_steps: int = 0
+    lr_min_ratio: float = 0.0
 
 
 class MLP:
@@ -35,7 +41,9 @@ class MLP:
         self.cpad = align(cfg.classes)
         self.layers.append(Linear(self.layout, "out", dims[-1], cfg.classes, n_pad=self.cpad))
         self.table = DenseTable(comm, self.layout.size, optimizer=cfg.optimizer, lr=cfg.lr,
-                                consistency=cfg.consistency, staleness=cfg.staleness)
+                                consistency=cfg.consistency, staleness=cfg.staleness,
+                                clip_norm=cfg.clip_norm,
+                                lr_schedule=lr_schedule_from(cfg.lr_warmup, cfg.lr_decay_steps, cfg.lr_min_ratio))
         g = torch.Generator().manual_seed(cfg.seed)
         full = torch.zeros(self.layout.size)
         for l in self.layers:

@@ -1,8 +1,9 @@
 """Data-plane ops of minips_amd.
 
 Every op has ONE device implementation: GPU tensors go to the hand-written gfx950 HIP
-kernels in ``minips_amd._kernels`` (and raise if that extension is missing -- there is no
-silent eager fallback on a GPU). CPU tensors run a plain PyTorch reference of the same math;
+kernels in ``minips_amd._kernels`` (the evaluation and gradient-clipping ops: in the small
+extensions ``_evalk`` / ``_optk``) and raise if that extension is missing -- there is no
+silent eager fallback on a GPU. CPU tensors run a plain PyTorch reference of the same math;
 that path exists for the CPU/gloo plumbing configuration (BASELINE config 1) and as the fp32
 oracle the GPU numerics tests compare against.
 """
@@ -12,7 +13,7 @@ import math
 
 import torch
 
-from .._native import evalk, kernels
+from .._native import evalk, kernels, optk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -729,6 +730,83 @@ def adam_apply(w, m, v, g, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.
         w_bf16.copy_(w.to(torch.bfloat16))
     if zero_g:
         g_in.zero_()
+
+
+# ----------------------------------------------------------------------------- global-norm clipping
+def _slab_args(slabs):
+    return [(s, int(n), int(p), int(o)) for s, n, p, o in slabs]
+
+
+def _fold_slabs(g, slabs):
+    """The fp32 gradient the Adam consumes: g + its split-K planes in the Adam kernel's order (groups of
+    four planes as (a0+a1)+(a2+a3), then the remainder one by one). ``g`` itself when there are none."""
+    if not slabs:
+        return g
+    x = g.clone()
+    for s, n, p, o in slabs:
+        P, r = s[: n * p].view(n, p), x[o: o + p]
+        z = 0
+        while z + 3 < n:
+            r += (P[z] + P[z + 1]) + (P[z + 2] + P[z + 3])
+            z += 4
+        while z < n:
+            r += P[z]
+            z += 1
+    return x
+
+
+def grad_sumsq(g, part, L=None, slabs=()):
+    """part[0:L] (fp64) = partial sums of squares of the fp32 gradient ``g`` (+ ``slabs``, as adam_apply's),
+    squared and accumulated in fp64: their sum is the squared l2 norm, non-finite exactly when an element is.
+    GPU: workgroup b of L writes part[b] -- no atomics, a function of the data and L only (g.numel() % 4 == 0,
+    16-byte aligned, 1 <= L <= 1024). CPU: the whole sum lands in part[0]."""
+    L = part.numel() if L is None else int(L)
+    if _gpu(g):
+        optk().grad_sumsq(g, _slab_args(slabs), part, L)
+        return part
+    if not 1 <= L <= 1024 or part.numel() < L or part.dtype != torch.float64:
+        raise RuntimeError(f"grad_sumsq: part must be float64 with 1 <= L <= 1024 entries, got {part.dtype} "
+                           f"[{part.numel()}], L {L}")
+    part[:L] = 0
+    part[0] = _fold_slabs(g, slabs).double().square().sum()
+    return part
+
+
+def clip_scale(total: float, max_norm: float):
+    """The rule's host form: (norm, scale, skip) of a squared norm ``total``. scale is torch's
+    clip_grad_norm_ coefficient max_norm / (norm + 1e-6), rounded to fp32 below 1, else exactly 1."""
+    if not math.isfinite(total):
+        return math.sqrt(total) if total > 0 else float("nan"), 0.0, True
+    norm = math.sqrt(total)
+    sd = max_norm / (norm + 1e-6)
+    return norm, (float(torch.tensor(sd, dtype=torch.float32)) if sd < 1.0 else 1.0), False
+
+
+def adam_clip_apply(w, m, v, g, lr, part, max_norm, stats, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                    step=1, np=None, w_bf16=None, step_dev=None, zero_g=False, slabs=(), write_stats=True):
+    """adam_apply with the gradient clipped to the global l2 norm ``max_norm``. total = sum(part[0:np]) (the
+    grad_sumsq partials of the WHOLE gradient, every bucket and rank; np <= 4096) is folded on the device in
+    one fixed order; scale = clip_scale(total); the update is adam_apply's with grad_scale = scale. A
+    non-finite total skips the clock: w, m, v and w_bf16 stay bit for bit, ``g`` is still cleared on
+    ``zero_g``. ``stats`` (fp64 [4]: norm, scale, n_clipped, n_skipped; scale 0 on a skip) is updated when
+    ``write_stats``. No host sync on the GPU."""
+    np = part.numel() if np is None else int(np)
+    if _gpu(w):
+        optk().adam_clip_apply(w, m, v, g, _slab_args(slabs), float(lr), float(beta1), float(beta2), float(eps),
+                               float(weight_decay), int(step), step_dev, w_bf16, bool(zero_g), part, np,
+                               float(max_norm), stats, bool(write_stats))
+        return
+    if not 1 <= np <= 4096 or part.numel() < np:
+        raise RuntimeError(f"adam_clip_apply: np {np} outside [1, 4096] or beyond part [{part.numel()}]")
+    norm, scale, skip = clip_scale(float(part[:np].sum()), float(max_norm))
+    if write_stats:
+        stats[0], stats[1] = norm, scale
+        stats[3 if skip else 2] += 1.0 if skip or scale < 1.0 else 0.0
+    if not skip:
+        adam_apply(w, m, v, _fold_slabs(g, slabs), lr, beta1, beta2, eps, weight_decay, step, scale, w_bf16,
+                   step_dev=step_dev)
+    if zero_g:
+        g.zero_()
 
 
 def slab_pack(g, out, slabs=()):

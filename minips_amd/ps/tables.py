@@ -180,6 +180,48 @@ def merge_buckets(starts, n_params: int, min_elems: float) -> list:
     return [0] + sorted(cuts)
 
 
+@dataclass
+class LRSchedule:
+    """Linear warmup + cosine decay of a learning rate, on the host in Python floats:
+    ``lr(step, base)`` = base * step / warmup for step <= warmup, then a half cosine from base down to
+    min_ratio * base at ``decay_steps``, constant after that (``decay_steps`` 0: no decay). ``step`` is the
+    1-based clock a DenseTable applies, so a restored table (finish_restore) resumes it exactly."""
+    warmup: int = 0
+    decay_steps: int = 0
+    min_ratio: float = 0.0
+
+    def __post_init__(self):
+        if self.warmup < 0 or self.decay_steps < 0 or not 0.0 <= self.min_ratio <= 1.0:
+            raise ValueError(f"LRSchedule: warmup {self.warmup}, decay_steps {self.decay_steps}, "
+                             f"min_ratio {self.min_ratio}")
+        if self.decay_steps and self.decay_steps <= self.warmup:
+            raise ValueError(f"LRSchedule: decay_steps {self.decay_steps} must exceed warmup {self.warmup}")
+
+    def lr(self, step: int, base: float = 1.0) -> float:
+        step = int(step)
+        if step < self.warmup:
+            return base * step / self.warmup
+        if not self.decay_steps or step <= self.warmup:
+            return base
+        if step >= self.decay_steps:
+            return self.min_ratio * base
+        t = (step - self.warmup) / (self.decay_steps - self.warmup)
+        return base * (self.min_ratio + (1.0 - self.min_ratio) * 0.5 * (1.0 + math.cos(math.pi * t)))
+
+
+def lr_schedule_from(warmup: int, decay_steps: int, min_ratio: float):
+    """The models' config fields -> an LRSchedule, or None when they are at their defaults."""
+    return LRSchedule(int(warmup), int(decay_steps), float(min_ratio)) if warmup or decay_steps else None
+
+
+# partial sums of squares per gradient piece (clip_norm): one grad_sumsq workgroup per 8192 elements, at most
+# _SUMSQ_MAX_L per piece and _CLIP_PARTS in all (every workgroup of every adam_clip_apply folds them all;
+# the kernel's limit is 4096)
+_SUMSQ_ELEMS = 8192
+_SUMSQ_MAX_L = 512
+_CLIP_PARTS = 2048
+
+
 # WGRAD_DEFER off: split-K weight gradients of one rank reduce into the gradient buffer (a
 # reduce kernel per GEMM) instead of being folded by the Adam kernel
 _WGRAD_DEFER = True
@@ -247,7 +289,8 @@ class DenseTable:
     def __init__(self, comm: Comm, n_params: int, optimizer: str = "adam", lr: float = 1e-3,
                  pull_dtype=torch.bfloat16, consistency: str = "bsp", staleness: int = 0, table_id: int = 0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, p2p: bool = False,
-                 value_dtype=torch.float32, buckets=None, overlap_w1: bool = False, bucket_mb: float | None = None):
+                 value_dtype=torch.float32, buckets=None, overlap_w1: bool = False, bucket_mb: float | None = None,
+                 clip_norm: float | None = None, lr_schedule: LRSchedule | None = None):
         """``value_dtype`` float64 gives the reference's ``double`` tables (KVClientTable<double>
         with VectorStorage::SubAdd, server/vector_storage.hpp:28-38): optimizer "add" only, pulled
         in fp64, so BSP sums are exact for exactly representable deltas.
@@ -269,13 +312,37 @@ class DenseTable:
         ``overlap_w1``: at world 1 too, run the clock on the table's side stream and, with
         ``buckets``, apply each bucket as soon as the backward finished its layer (one rank has
         no communication to hide, but the per-bucket optimizer then overlaps the remaining
-        backward instead of running after it)."""
+        backward instead of running after it).
+
+        ``clip_norm`` (Adam on fp32 values): every clock clips the gradient to this global l2 norm, torch's
+        clip_grad_norm_ rule, as a device-side part of the clock. One extra read pass over the reduced shard
+        leaves fp64 partial sums of squares (ops.grad_sumsq), several ranks add ONE small all-reduce of
+        those partials (after the last reduce-scatter, before the first all-gather), and the Adam kernel
+        derives the scale from them (ops.adam_clip_apply): no host sync, the same bits on every rank,
+        launch and HIP-graph replay. A clock whose gradient holds an inf or a NaN is skipped: master, m, v
+        and the parameters stay bit for bit, the gradient is cleared as usual, and the step counter still
+        advances (Adam's t counts clocks, applied or not). With buckets the reduce-scatters keep their
+        overlap with the backward, but the norm needs every bucket, so the Adams and all-gathers move
+        behind the last bucket: clock() runs them in bucket order. clip_stats() reads the norm, the scale
+        and the clipped / skipped counters; the counters are not checkpointed (a restored table counts
+        from zero).
+
+        ``lr_schedule`` (an LRSchedule): the optimizer's lr of clock ``step`` is lr_schedule.lr(step, lr),
+        computed on the host, for every optimizer. A clock captured in a HIP graph would bake one value
+        in, so a schedule raises RuntimeError inside a capture; clipping alone captures fine."""
         if value_dtype not in (torch.float32, torch.float64):
             raise ValueError(f"value_dtype {value_dtype}")
         if value_dtype == torch.float64:
             if optimizer != "add":
                 raise ValueError("fp64 dense tables support the reference's plain add apply only")
             pull_dtype = torch.float64
+        if clip_norm is not None:
+            if optimizer != "adam" or value_dtype != torch.float32:
+                raise ValueError("clip_norm needs optimizer='adam' on fp32 values")
+            if not float(clip_norm) > 0.0:
+                raise ValueError(f"clip_norm {clip_norm}: a positive norm")
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.lr_schedule = lr_schedule
         self.value_dtype = value_dtype
         self.comm = comm
         self.table_id = table_id
@@ -310,6 +377,49 @@ class DenseTable:
             buckets = merge_buckets(buckets, n_params, bucket_mb * 2**20 / self.master.element_size())
         if buckets is not None and (comm.world > 1 or self.pipe.async_):
             self._init_buckets(buckets)
+        if self.clip_norm is not None:
+            self._init_clip()
+
+    # -- clipping / schedule -------------------------------------------------------------------
+    def _init_clip(self):
+        """One fp64 partial buffer with a slice per bucket (one for the flat table): slice lengths follow
+        from the piece sizes alone, so every rank and every run lays the sums out alike."""
+        sizes = [sz for _, sz in self._boff] if self.buckets is not None else [self.shard]
+        cap = min(_SUMSQ_MAX_L, _CLIP_PARTS // len(sizes))
+        if cap < 1:
+            raise ValueError(f"clip_norm: {len(sizes)} buckets, at most {_CLIP_PARTS} (use bucket_mb)")
+        self._clip_sl, off = [], 0
+        for sz in sizes:
+            L = max(1, min(cap, -(-sz // _SUMSQ_ELEMS)))
+            self._clip_sl.append((off, L))
+            off += L
+        dev = self.comm.device
+        self._clip_part = torch.zeros(off, dtype=torch.float64, device=dev)
+        self._clip_stats = torch.zeros(4, dtype=torch.float64, device=dev)  # norm, scale, clipped, skipped
+        self._clip_todo: list = []  # the buckets whose Adam waits for the norm
+
+    def clip_stats(self) -> dict:
+        """Drain the clocks and read the last clock's gradient norm and clip scale (0 on a skipped clock)
+        and how many clocks were clipped / skipped so far: the one host read of clipping."""
+        if self.clip_norm is None:
+            raise RuntimeError("clip_stats: the table was built without clip_norm")
+        self.drain()
+        norm, scale, clipped, skipped = self._clip_stats.tolist()
+        return dict(norm=norm, scale=scale, clipped=int(clipped), skipped=int(skipped))
+
+    def lr_at(self, step: int) -> float:
+        """The optimizer's lr of clock ``step`` (1-based)."""
+        if self.lr_schedule is None:
+            return self.lr
+        if self.master.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("lr_schedule inside a HIP-graph capture: the captured clock would replay one lr")
+        return self.lr_schedule.lr(step, self.lr)
+
+    def _adam_clip(self, w, m, v, gs, step, out, sd, zero_g, slabs, write_stats=True):
+        """The clipping Adam on one piece, once the clock's partial sums are complete."""
+        ops.adam_clip_apply(w, m, v, gs, self.lr_at(step), self._clip_part, self.clip_norm, self._clip_stats,
+                            self.betas[0], self.betas[1], self.eps, self.weight_decay, step, w_bf16=out, step_dev=sd,
+                            zero_g=zero_g, slabs=slabs, write_stats=write_stats)
 
     # -- bucketed clocks ----------------------------------------------------------------------
     def _init_buckets(self, starts):
@@ -404,16 +514,23 @@ class DenseTable:
             gs = gs_own
         out = p_own if self.pull_dtype == torch.bfloat16 else None
         zeroed = False
+        lr = self.lr if self.lr_schedule is None else self.lr_at(step)
         if self.optimizer == "adam":
             sink = getattr(self, "_sink", None)  # (one rank: the bucket's split-K wgrad planes)
             slabs = sink.take(gs) if sink is not None and local else ()
-            ops.adam_apply(w, m, v, gs, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, step, 1.0,
+            if self.clip_norm is not None:
+                # the bucket's share of the norm now; its Adam and all-gather once the norm is whole
+                o, L = self._clip_sl[k]
+                ops.grad_sumsq(gs, self._clip_part[o: o + L], L, slabs)
+                self._clip_todo.append((k, gs, slabs, sd, local, packed))
+                return
+            ops.adam_apply(w, m, v, gs, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, step, 1.0,
                            out, step_dev=sd, zero_g=local, slabs=slabs)
             zeroed = local or packed  # the kernel (or the pack) cleared the gradient
         elif self.optimizer == "adagrad":
-            ops.adagrad_apply(w, m, gs, self.lr, self.eps, 1.0, out)
+            ops.adagrad_apply(w, m, gs, lr, self.eps, 1.0, out)
         elif self.optimizer == "sgd":
-            ops.sgd_apply(w, gs, self.lr, 1.0, out)
+            ops.sgd_apply(w, gs, lr, 1.0, out)
         elif self.optimizer == "add":
             w.add_(gs)
             if out is not None:
@@ -422,18 +539,39 @@ class DenseTable:
             raise ValueError(self.optimizer)
         if out is None:
             p_own.copy_(w)
+        self._bucket_finish(k, g_b, p_b, p_own, zeroed or packed)
+
+    def _bucket_finish(self, k, g_b, p_b, p_own, cleared):
+        comm = self.comm
         comm.all_gather(p_b, p_own)
-        if not (zeroed or packed):
+        if not cleared:
             g_b.zero_()
         key, nb = self._bstat[k]
         bb = comm.stats.bucket_bytes
         bb[key] = bb.get(key, 0) + nb
 
+    def _clip_buckets(self, grad: torch.Tensor, step: int):
+        """The clipped clock's second half, once every bucket's partial sums are in: the one all-reduce
+        of the partials, then Adam + all-gather per bucket in index order."""
+        todo, self._clip_todo = sorted(self._clip_todo, key=lambda e: e[0]), []
+        if not todo:
+            return
+        self.comm.all_reduce_(self._clip_part)
+        for i, (k, gs, slabs, sd, local, packed) in enumerate(todo):
+            g_b, _, w, m, v, p_own, p_b = self._bucket_views(k, grad)
+            out = p_own if self.pull_dtype == torch.bfloat16 else None
+            self._adam_clip(w, m, v, gs, step, out, sd, local, slabs, write_stats=i == 0)
+            if out is None:
+                p_own.copy_(w)
+            self._bucket_finish(k, g_b, p_b, p_own, local or packed)
+
     @traced("dense.bucket_ready")
     def bucket_ready(self, k: int, events=()):
         """The gradients of bucket ``k`` are complete (every writer is on the current stream or
         behind ``events``): issue its reduce-scatter + apply + all-gather now (on the clock
-        stream when clocks are asynchronous, so it overlaps the rest of the backward)."""
+        stream when clocks are asynchronous, so it overlaps the rest of the backward). With
+        ``clip_norm`` only the reduce-scatter and the bucket's partial sums of squares are issued here;
+        the apply and the all-gather need the whole norm and follow in clock()."""
         if self.buckets is None or k in self._issued:
             return
         self._pending = True  # the gradients were written in place into self.grad
@@ -527,6 +665,8 @@ class DenseTable:
                     for k in range(len(self.buckets)):
                         if k not in self._issued:
                             self._bucket_work(k, grad, step)
+                    if self.clip_norm is not None:
+                        self._clip_buckets(grad, step)
                 else:
                     self._step_dev_for_clock()
                 self._issued = set()
@@ -591,18 +731,23 @@ class DenseTable:
     def _apply(self, g: torch.Tensor, step: int, zero_g: bool = False, step_dev=None) -> bool:
         """Apply the optimizer to the owned shard; True if ``g`` was cleared on the way."""
         out = self.params[self.base: self.base + self.shard] if self.pull_dtype == torch.bfloat16 else None
+        lr = self.lr if self.lr_schedule is None else self.lr_at(step)
         if self.optimizer == "adam":
             sink = getattr(self, "_sink", None)
-            slabs = sink.take(g) if sink is not None else ()
-            ops.adam_apply(self.master, self.m, self.v, g, self.lr, self.betas[0], self.betas[1], self.eps,
-                           self.weight_decay, step, 1.0, out, step_dev=step_dev, zero_g=zero_g, slabs=slabs)
+            slabs = sink.take(g) if sink is not None else ()  # (taken once: both kernels fold the same planes)
+            if self.clip_norm is None:
+                ops.adam_apply(self.master, self.m, self.v, g, lr, self.betas[0], self.betas[1], self.eps,
+                               self.weight_decay, step, 1.0, out, step_dev=step_dev, zero_g=zero_g, slabs=slabs)
+            else:
+                self.comm.all_reduce_(ops.grad_sumsq(g, self._clip_part, slabs=slabs))
+                self._adam_clip(self.master, self.m, self.v, g, step, out, step_dev, zero_g, slabs)
             if out is None:
                 self.params[self.base: self.base + self.shard].copy_(self.master)
             return zero_g
         elif self.optimizer == "adagrad":
-            ops.adagrad_apply(self.master, self.m, g, self.lr, self.eps, 1.0, out)
+            ops.adagrad_apply(self.master, self.m, g, lr, self.eps, 1.0, out)
         elif self.optimizer == "sgd":
-            ops.sgd_apply(self.master, g, self.lr, 1.0, out)
+            ops.sgd_apply(self.master, g, lr, 1.0, out)
         elif self.optimizer == "add":  # the reference server apply: w += delta
             self.master.add_(g)
             if out is not None:
@@ -630,6 +775,8 @@ class DenseTable:
         self.pipe.reset()
         self._pending = False
         self.__dict__.pop("_held", None)
+        if self.clip_norm is not None:
+            self._clip_todo = []
         for g in self._ring:
             g.zero_()
 

@@ -103,7 +103,23 @@ def parse(argv=None):
     ap.add_argument("--eval_batches", type=int, default=4, help="held-out batches per rank and evaluation")
     ap.add_argument("--eval_seed", type=int, default=12345,
                     help="seed of the held-out stream (re-created at every evaluation: the same batches each time)")
+    ap.add_argument("--clip_norm", type=float, default=0.0,
+                    help="> 0: clip the gradient to this global l2 norm in every dense clock (gpt2 / mlp; a clock "
+                         "whose gradient is not finite is skipped); 0: off, nothing changes")
+    ap.add_argument("--lr_warmup", type=int, default=0, help="linear lr warmup over this many steps (gpt2 / mlp)")
+    ap.add_argument("--lr_decay_steps", type=int, default=0,
+                    help="> 0: cosine lr decay from the end of the warmup down to --lr_min_ratio at this step")
+    ap.add_argument("--lr_min_ratio", type=float, default=0.0, help="final lr / peak lr of the cosine decay")
     args = ap.parse_args(argv)
+    args.opt_flags = bool(args.clip_norm or args.lr_warmup or args.lr_decay_steps or args.lr_min_ratio)
+    if args.opt_flags and args.model not in ("gpt2", "mlp"):
+        ap.error(f"--clip_norm / --lr_warmup / --lr_decay_steps / --lr_min_ratio support --model gpt2 and mlp, "
+                 f"not {args.model}")
+    if args.clip_norm < 0 or args.lr_warmup < 0 or args.lr_decay_steps < 0 or not 0 <= args.lr_min_ratio <= 1 \
+            or (args.lr_decay_steps and args.lr_decay_steps <= args.lr_warmup):
+        ap.error("--clip_norm >= 0, 0 <= --lr_warmup < --lr_decay_steps (or no decay), 0 <= --lr_min_ratio <= 1")
+    if args.lr_min_ratio and not args.lr_decay_steps:
+        ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
     if args.eval_every > 0 and args.model not in ("widedeep", "dlrm"):
@@ -148,6 +164,12 @@ SMALL_CARDS = [50, 7, 300, 20, 5, 60, 90, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19
                28]
 
 
+def _opt_kw(args) -> dict:
+    """--clip_norm / --lr_* as GPT2Config / MLPConfig fields."""
+    return dict(clip_norm=args.clip_norm or None, lr_warmup=args.lr_warmup, lr_decay_steps=args.lr_decay_steps,
+                lr_min_ratio=args.lr_min_ratio)
+
+
 def build(args, comm):
     """-> (model, tables {id: table}, make_data() -> a fresh data stream with next()/skip(), step
     fn(batch) -> loss, samples/step). A fresh stream + skip(k) repositions the data at iteration k
@@ -169,7 +191,7 @@ def build(args, comm):
         from .data.synthetic import MnistSynth
         from .models.mlp import MLP, MLPConfig
 
-        m = MLP(MLPConfig(consistency=args.consistency, staleness=args.staleness), comm)
+        m = MLP(MLPConfig(consistency=args.consistency, staleness=args.staleness, **_opt_kw(args)), comm)
         B = args.batch or (64 if args.small else 8192)
         return m, {0: m.table}, (lambda: _Skippable(MnistSynth(B, device=dev, seed=seed))), \
             (lambda b: m.train_step(*b)[0]), B
@@ -187,7 +209,7 @@ def build(args, comm):
         from .models.gpt2 import GPT2, GPT2Config
 
         kw = dict(vocab=500, n_ctx=64, d=128, n_layer=2, n_head=2) if args.small else {}
-        cfg = GPT2Config(consistency=args.consistency, staleness=args.staleness, **kw)
+        cfg = GPT2Config(consistency=args.consistency, staleness=args.staleness, **_opt_kw(args), **kw)
         m = GPT2(cfg, comm)
         B = args.batch or (2 if args.small else 8)
         return m, {0: m.table}, (lambda: _Skippable(TokenSynth(B, cfg.n_ctx, vocab=cfg.vocab, device=dev,             \
@@ -626,9 +648,17 @@ def main(argv=None):
                 with comm.waiting():
                     lv = float(loss.float().sum()) / per_step
                 losses.append((it, lv))
-                log.step(it, per_step, time.perf_counter() - t0, comm.stats, loss=lv)
+                opt = {}
+                if args.opt_flags:  # (read at report intervals only: clip_stats() drains the clock)
+                    tab = tables[0]
+                    opt["lr"] = tab.lr_at(tab.step)
+                    if tab.clip_norm is not None:
+                        cs = tab.clip_stats()
+                        opt.update(grad_norm=cs["norm"], clip_scale=cs["scale"])
+                log.step(it, per_step, time.perf_counter() - t0, comm.stats, loss=lv, **opt)
                 if rank == 0:
-                    print(f"Current iteration={it + 1} on node={rank} loss={lv:.5f}", flush=True)
+                    print(f"Current iteration={it + 1} on node={rank} loss={lv:.5f}"
+                          + "".join(f" {k}={v:.6g}" for k, v in opt.items()), flush=True)
             if report and (it + 1) % args.report_interval == 0:
                 report.write(f"{it + 1}\t{(time.perf_counter() - t_start) * 1e3:.1f}\n")
                 report.flush()
@@ -672,13 +702,17 @@ def main(argv=None):
         torch.cuda.synchronize(comm.device)
     if hb:
         hb.stop()
+    clip_final = {}
+    if args.clip_norm:
+        cs = tables[0].clip_stats()
+        clip_final = dict(clipped_steps=cs["clipped"], skipped_steps=cs["skipped"])
     if comm.rank == 0:
         print(json.dumps(dict(model=args.model, steps=args.steps, start=start, losses=losses,
                               checksum=[round(float(x), 6) for x in sums.cpu()],
                               total_ms=round((time.perf_counter() - t_start) * 1e3, 1),
                               steady_ms_per_iter=round(steady_ms, 4) if steady_ms is not None else None,
                               world=comm.world, generation=generation,
-                              **({"evals": evals} if args.eval_every > 0 else {}))),
+                              **({"evals": evals} if args.eval_every > 0 else {}), **clip_final)),
               flush=True)
     if comm.world > 1:
         comm.barrier()

@@ -53,11 +53,12 @@ def build(args, comm):
         from minips_amd.models.gpt2 import GPT2, GPT2Config
 
         B, T = args.batch or 8, args.seq
-        m = GPT2(GPT2Config(consistency=args.consistency, staleness=args.staleness), comm)
+        m = GPT2(GPT2Config(consistency=args.consistency, staleness=args.staleness,
+                            clip_norm=args.clip_norm or None), comm)
         data = TokenSynth(B, T, device=dev, seed=r)
         return m, (lambda: m.train_step(*data.next())), B * T, "tokens/s", \
             dict(model="GPT-2 small 124M (12L/768d/12H, vocab 50257), dense params sharded over PS ranks",
-                 seq_len=T, batch_per_gpu=B)
+                 seq_len=T, batch_per_gpu=B, **({"clip_norm": args.clip_norm} if args.clip_norm else {}))
     if args.model in ("dlrm", "dlrm-10b"):
         from minips_amd.models.dlrm import DLRM, DLRMConfig
 
@@ -170,7 +171,11 @@ def main():
                          "the model's default (DLRM SSP/ASP: onesided; widedeep-ssp: collective)")
     ap.add_argument("--value-dtype", default="float32", choices=["float32", "float64"],
                     help="lr: table precision (float64 = the reference's CreateTable<double>)")
+    ap.add_argument("--clip-norm", "--clip_norm", dest="clip_norm", type=float, default=0.0,
+                    help="gpt2: > 0 clips the gradient to this global l2 norm in every clock (0: off)")
     args = ap.parse_args()
+    if args.clip_norm and args.model != "gpt2":
+        ap.error("--clip_norm: --model gpt2 only")
     if args.transport == "auto" and not args.model.startswith("dlrm"):
         args.transport = "collective"
     from minips_amd.ps.comm import init_distributed

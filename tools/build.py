@@ -11,6 +11,8 @@ Targets
   ops_py    csrc/bindings/ops_py.cpp     -> minips_amd/_kernels*.so   (hipcc, torch headers)
   eval_py   csrc/bindings/eval_py.cpp    -> minips_amd/_evalk*.so     (the held-out evaluation ops: a second,
             small torch extension that links k_evalmetrics.o only)
+  optim_py  csrc/bindings/optim_py.cpp   -> minips_amd/_optk*.so      (global-norm gradient clipping: a third
+            small torch extension, over k_gradclip.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -199,19 +201,29 @@ def build_ops_py(kobjs: list[str], robjs: list[str] = ()) -> str:
     return out
 
 
-def build_eval_py(kobjs: list[str]) -> str:
-    """minips_amd/_evalk: the evaluation bindings over k_evalmetrics.o alone."""
-    src = os.path.join(ROOT, "csrc/bindings/eval_py.cpp")
-    out = os.path.join(PKG, "_evalk" + EXT)
-    bobj = os.path.join(OBJ, "eval_py.o")
-    cflags, ldflags = _torch_flags("_evalk")
-    kobjs = [o for o in kobjs if os.path.basename(o) == "k_evalmetrics.o"]
+def _build_small_ext(kobjs: list[str], src_name: str, mod: str, kernel_obj: str) -> str:
+    """A small torch extension minips_amd/<mod>: one binding file over one kernel object."""
+    src = os.path.join(ROOT, "csrc/bindings", src_name + ".cpp")
+    out = os.path.join(PKG, mod + EXT)
+    bobj = os.path.join(OBJ, src_name + ".o")
+    cflags, ldflags = _torch_flags(mod)
+    kobjs = [o for o in kobjs if os.path.basename(o) == kernel_obj]
     hdrs = _headers("csrc/kernels", "csrc/bindings")
     _compile_many([(bobj, [src] + hdrs, [HIPCC, "-O2", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}",
                                          *cflags, "-c", src, "-o", bobj])])
     _compile_many([(out, [bobj] + kobjs,
                     [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", bobj, *kobjs, "-o", out, *ldflags])])
     return out
+
+
+def build_eval_py(kobjs: list[str]) -> str:
+    """minips_amd/_evalk: the evaluation bindings over k_evalmetrics.o alone."""
+    return _build_small_ext(kobjs, "eval_py", "_evalk", "k_evalmetrics.o")
+
+
+def build_optim_py(kobjs: list[str]) -> str:
+    """minips_amd/_optk: the gradient-clipping bindings over k_gradclip.o alone."""
+    return _build_small_ext(kobjs, "optim_py", "_optk", "k_gradclip.o")
 
 
 def build_sanitized(kind: str) -> list[str]:
@@ -240,7 +252,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 
 def main(argv: list[str]) -> int:
-    targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py"}
+    targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -256,13 +268,15 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py", "eval_py"}:
+    if targets & {"kernels", "ops_py", "eval_py", "optim_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
             print("built", build_ops_py(kobjs + comm_objs(), objs))
         if targets & {"kernels", "eval_py"}:
             print("built", build_eval_py(kobjs))
+        if targets & {"kernels", "optim_py"}:
+            print("built", build_optim_py(kobjs))
     return 0
 
 
