@@ -18,10 +18,6 @@ using namespace minips_access;  // NOLINT: the accessors are this file's vocabul
 using OptTensor = c10::optional<at::Tensor>;
 using DeviceGuard = c10::hip::HIPGuardMasqueradingAsCUDA;
 
-hipStream_t stream_of(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-
 // acc: neg[NB] | pos[NB] | loss_fx | n_nan -> NB
 int bins_of(const at::Tensor& acc) {
   const int64_t n = acc.numel();
@@ -30,10 +26,6 @@ int bins_of(const at::Tensor& acc) {
               "acc holds ", n, " elements, expected 2*NB + 2 with NB a power of two in [", minips_k::kEvalMinBins,
               ", ", minips_k::kEvalMaxBins, "]");
   return (int)NB;
-}
-
-void aligned16(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
 }
 
 void binary_hist(const at::Tensor& logits, const at::Tensor& labels, at::Tensor& acc) {

@@ -30,10 +30,6 @@ using namespace minips_access;  // NOLINT: the accessors are this file's vocabul
 using OptTensor = c10::optional<at::Tensor>;
 using DeviceGuard = c10::hip::HIPGuardMasqueradingAsCUDA;
 
-hipStream_t stream_of(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-
 // Several outputs carved out of ONE caching-allocator block (256-byte aligned views): a planner
 // call hands back ~10 tensors, and one allocation + views costs a fraction of ten allocations on
 // the step's host path. The block lives while any of its views does.
@@ -61,25 +57,6 @@ const int64_t* dev_count(const OptTensor& n_dev, const char* name = "n_dev") {
 
 // a row-major fp32 table shard [rows, >= cols] (the caller reads stride(0))
 float* dev_table(const at::Tensor& table, int64_t cols = 0) { return dev_rows<float>(table, "table", 0, cols); }
-
-// (slab [nsplit * plane] fp32, nsplit, plane, offset of its region in the gradient): split-K planes
-// left unreduced by gemm_slab; each region's length is its plane and lies inside [0, region_len)
-using SlabList = std::vector<std::tuple<at::Tensor, int64_t, int64_t, int64_t>>;
-minips_k::AdamSlabs parse_slabs(const SlabList& slabs, int64_t region_len, const char* what) {
-  minips_k::AdamSlabs sl;
-  TORCH_CHECK(slabs.size() <= 4, what, ": at most 4 slab regions");
-  for (const auto& t : slabs) {
-    const int64_t ns = std::get<1>(t), plane = std::get<2>(t), off = std::get<3>(t);
-    TORCH_CHECK(ns >= 1 && plane >= 0 && off >= 0 && off + plane <= region_len, what, ": slabs region bounds");
-    sl.p[sl.n] = dev<float>(std::get<0>(t), "slabs plane", ns * plane);
-    sl.nsplit[sl.n] = (int)ns;
-    sl.plane[sl.n] = plane;
-    sl.len[sl.n] = plane;
-    sl.off[sl.n] = off;
-    ++sl.n;
-  }
-  return sl;
-}
 
 // the requesters' segments of the received rows: segment p = rows [off[p], off[p+1])
 minips_k::OwnerSegs owner_segs(const std::vector<int64_t>& splits, int64_t* total) {
@@ -753,7 +730,7 @@ void adam_apply(at::Tensor& w, at::Tensor& m, at::Tensor& v, const at::Tensor& g
   const int64_t n = w.numel();
   TORCH_CHECK(n == m.numel() && n == v.numel() && n == g.numel(), "adam sizes differ: w, m, v, g");
   TORCH_CHECK(!present(w_bf16) || w_bf16->numel() == n, "w_bf16 size");
-  const minips_k::AdamSlabs sl = parse_slabs(slabs, n, "adam");
+  const minips_k::AdamSlabs sl = parse_slabs(slabs, n, "adam_apply");
   DeviceGuard gd(gpu_of(w, "w"));
   minips_k::adam_apply(dev<float>(w, "w"), dev<float>(m, "m"), dev<float>(v, "v"), dev<float>(g, "g"), n, (float)lr,
                        (float)beta1, (float)beta2, (float)eps, (float)weight_decay, (int)step, (float)grad_scale,

@@ -9,8 +9,6 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
 
-#include <tuple>
-
 #include "../kernels/gradclip.h"
 #include "tensor_access.h"
 
@@ -21,38 +19,6 @@ using namespace minips_access;  // NOLINT: the accessors are this file's vocabul
 using OptTensor = c10::optional<at::Tensor>;
 using DeviceGuard = c10::hip::HIPGuardMasqueradingAsCUDA;
 
-hipStream_t stream_of(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
-}
-
-void aligned16(const at::Tensor& t, const char* name) {
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
-}
-
-// (slab [nsplit * plane] fp32, nsplit, plane, offset of its region in the gradient), as adam_apply's:
-// each region's length is its plane and lies inside [0, region_len)
-using SlabList = std::vector<std::tuple<at::Tensor, int64_t, int64_t, int64_t>>;
-minips_k::AdamSlabs parse_slabs(const SlabList& slabs, int64_t region_len) {
-  minips_k::AdamSlabs sl;
-  TORCH_CHECK(slabs.size() <= 4, "slabs: at most 4 slab regions");
-  for (const auto& t : slabs) {
-    const int64_t ns = std::get<1>(t), plane = std::get<2>(t), off = std::get<3>(t);
-    TORCH_CHECK(ns >= 1 && ns <= (1 << 20) && plane >= 0 && off >= 0 && off + plane <= region_len,
-                "slabs: region bounds (nsplit ", ns, ", plane ", plane, ", offset ", off, ") outside a gradient of ",
-                region_len, " elements");
-    TORCH_CHECK(plane % 4 == 0 && off % 4 == 0, "slabs: plane ", plane, " and offset ", off,
-                " must be multiples of 4");
-    sl.p[sl.n] = dev<float>(std::get<0>(t), "slabs plane", ns * plane);
-    aligned16(std::get<0>(t), "slabs plane");
-    sl.nsplit[sl.n] = (int)ns;
-    sl.plane[sl.n] = plane;
-    sl.len[sl.n] = plane;
-    sl.off[sl.n] = off;
-    ++sl.n;
-  }
-  return sl;
-}
-
 void grad_sumsq(const at::Tensor& g, const SlabList& slabs, at::Tensor& part, int64_t L) {
   const int64_t n = g.numel();
   TORCH_CHECK(L >= 1 && L <= minips_k::kSumsqMaxBlocks, "L is ", L, ", expected 1 <= L <= ",
@@ -61,7 +27,7 @@ void grad_sumsq(const at::Tensor& g, const SlabList& slabs, at::Tensor& part, in
   DeviceGuard gd(gpu_of(g, "g"));
   const float* gp = dev<float>(g, "g", n);
   aligned16(g, "g");
-  const minips_k::AdamSlabs sl = parse_slabs(slabs, n);
+  const minips_k::AdamSlabs sl = parse_slabs(slabs, n, "grad_sumsq");
   double* pp = dev<double>(part, "part", L);
   minips_k::grad_sumsq(gp, n, sl.n ? &sl : nullptr, pp, (int)L, stream_of(g));
 }
@@ -89,7 +55,7 @@ void adam_clip_apply(at::Tensor& w, at::Tensor& m, at::Tensor& v, at::Tensor& g,
   aligned16(m, "m");
   aligned16(v, "v");
   aligned16(g, "g");
-  const minips_k::AdamSlabs sl = parse_slabs(slabs, n);
+  const minips_k::AdamSlabs sl = parse_slabs(slabs, n, "adam_clip_apply");
   const int* sd = dev_opt<int>(step_dev, "step_dev", 1);
   bf16_t* wb = dev_opt<bf16_t>(w_bf16, "w_bf16", n);
   TORCH_CHECK(!wb || reinterpret_cast<uintptr_t>(wb) % 8 == 0, "w_bf16 must be 8-byte aligned");

@@ -8,11 +8,17 @@
 //   dev_opt_strided<T>(opt, "name", n) the same for a 1-D view of any positive stride (the caller reads stride(0))
 //   dev_rows_any(t, "name", &bf16, rows, cols)  contiguous fp32 or bf16 rows; says which it found
 //   dev_bytes(t, "name", nbytes)      any dtype (copies and collectives): GPU, contiguous, >= nbytes
+//   parse_slabs(list, n, "op")        the split-K slab list of a dense-clock op -> AdamSlabs inside n elements
+// stream_of(t) is the current HIP stream of t's device, aligned16(t, "name") the 16-byte check of float4 kernels.
 // The element counts are what the kernel will address, stated where the pointer is taken. The dtype
 // follows from T (dtype_of), never from a second argument that could disagree with the cast.
 #pragma once
 
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/extension.h>
+
+#include <tuple>
+#include <vector>
 
 #include "../kernels/kernels.h"
 
@@ -107,6 +113,39 @@ inline void* dev_bytes(const at::Tensor& t, const char* name, int64_t nbytes = 0
   TORCH_CHECK(nbytes >= 0 && t.numel() * (int64_t)t.element_size() >= nbytes, name, " holds ",
               t.numel() * (int64_t)t.element_size(), " bytes, the kernel addresses ", nbytes);
   return t.data_ptr();
+}
+
+inline hipStream_t stream_of(const at::Tensor& t) {
+  return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
+}
+
+inline void aligned16(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
+// (slab [nsplit * plane] fp32, nsplit, plane, offset of its region in the gradient): split-K planes left
+// unreduced by gemm_slab; each region's length is its plane and lies inside [0, region_len). Every message
+// names `slabs`, the argument (the validation tables look for it).
+using SlabList = std::vector<std::tuple<at::Tensor, int64_t, int64_t, int64_t>>;
+inline minips_k::AdamSlabs parse_slabs(const SlabList& slabs, int64_t region_len, const char* what) {
+  minips_k::AdamSlabs sl;
+  TORCH_CHECK(slabs.size() <= 4, what, ": slabs: at most 4 slab regions");
+  for (const auto& t : slabs) {
+    const int64_t ns = std::get<1>(t), plane = std::get<2>(t), off = std::get<3>(t);
+    TORCH_CHECK(ns >= 1 && ns <= (1 << 20) && plane >= 0 && off >= 0 && off + plane <= region_len, what,
+                ": slabs: region bounds (nsplit ", ns, ", plane ", plane, ", offset ", off,
+                ") outside a gradient of ", region_len, " elements");
+    TORCH_CHECK(plane % 4 == 0 && off % 4 == 0, what, ": slabs: plane ", plane, " and offset ", off,
+                " must be multiples of 4");
+    sl.p[sl.n] = dev<float>(std::get<0>(t), "slabs plane", ns * plane);
+    aligned16(std::get<0>(t), "slabs plane");
+    sl.nsplit[sl.n] = (int)ns;
+    sl.plane[sl.n] = plane;
+    sl.len[sl.n] = plane;
+    sl.off[sl.n] = off;
+    ++sl.n;
+  }
+  return sl;
 }
 
 }  // namespace minips_access

@@ -1,8 +1,10 @@
 // Global-norm gradient clipping as a device-side part of the dense clock (gradclip.hip; bindings in
 // csrc/bindings/optim_py.cpp, module minips_amd._optk).
 //
-// The rule, with x_i the fp32 gradient element the Adam consumes (g[i] plus its split-K planes, folded
-// in adam_kernel's order: groups of four as (a0+a1)+(a2+a3), then the remainder one by one):
+// The rule, with x_i the fp32 gradient element the Adam consumes (g[i] plus its split-K planes in the
+// grouped order slab_fold<true> of dense_update.h: groups of four as (a0+a1)+(a2+a3), then the remainder
+// one by one; the dense clock's other order, plane by plane, is only what slab_pack and ps_push_dense ship
+// and differs in rounding from 4 planes on):
 //   total  = sum_i (double)x_i * (double)x_i      (over every rank's shard; non-finite iff an element is)
 //   norm   = sqrt(total);  scale_d = max_norm / (norm + 1e-6)
 //   scale  = scale_d < 1 ? (float)scale_d : 1.0f

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "common.h"
+#include "dense_update.h"
 #include "gradclip.h"
 
 namespace minips_k {
@@ -13,34 +14,6 @@ namespace minips_k {
 namespace {
 
 constexpr int kBlock = 256;
-
-// the gradient element the Adam consumes: g + its split-K planes, adam_kernel's fold order
-__device__ __forceinline__ float4 fold_slabs(float4 Gs, int64_t i, const AdamSlabs& sl) {
-  for (int k = 0; k < sl.n; ++k) {
-    const int64_t e = 4 * i - sl.off[k];
-    if (e < 0 || e >= sl.len[k]) continue;
-    const float* p = sl.p[k] + e;
-    int z = 0;
-    for (; z + 3 < sl.nsplit[k]; z += 4) {
-      const float4 a0 = *reinterpret_cast<const float4*>(p + z * sl.plane[k]);
-      const float4 a1 = *reinterpret_cast<const float4*>(p + (z + 1) * sl.plane[k]);
-      const float4 a2 = *reinterpret_cast<const float4*>(p + (z + 2) * sl.plane[k]);
-      const float4 a3 = *reinterpret_cast<const float4*>(p + (z + 3) * sl.plane[k]);
-      Gs.x += (a0.x + a1.x) + (a2.x + a3.x);
-      Gs.y += (a0.y + a1.y) + (a2.y + a3.y);
-      Gs.z += (a0.z + a1.z) + (a2.z + a3.z);
-      Gs.w += (a0.w + a1.w) + (a2.w + a3.w);
-    }
-    for (; z < sl.nsplit[k]; ++z) {
-      const float4 a = *reinterpret_cast<const float4*>(p + z * sl.plane[k]);
-      Gs.x += a.x;
-      Gs.y += a.y;
-      Gs.z += a.z;
-      Gs.w += a.w;
-    }
-  }
-  return Gs;
-}
 
 // a float squared is exact in fp64 (48 significant bits), so the sum differs from any other order of
 // the same terms by rounding of the additions only
@@ -79,7 +52,7 @@ __global__ __launch_bounds__(kBlock) void grad_sumsq_kernel(const float* __restr
       a3 = sq_acc(a3, G3);
     }
   }
-  for (; i < n4; i += stride) a0 = sq_acc(a0, fold_slabs(g4[i], i, sl));
+  for (; i < n4; i += stride) a0 = sq_acc(a0, slab_fold<true>(g4[i], i, sl));
   const double t = block_sum((a0 + a1) + (a2 + a3), sh);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
@@ -123,44 +96,8 @@ __global__ __launch_bounds__(kBlock) void adam_clip_kernel(float* __restrict__ w
     bc1 = 1.f - powf(b1, t);
     bc2 = 1.f - powf(b2, t);
   }
-  // the element update: adam_kernel's (optim.hip), expression for expression
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    float4 W = reinterpret_cast<float4*>(w)[i], M = reinterpret_cast<float4*>(m)[i];
-    float4 V = reinterpret_cast<float4*>(v)[i];
-    const float4 G = reinterpret_cast<const float4*>(g)[i];
-    float* Wp = &W.x;
-    float* Mp = &M.x;
-    float* Vp = &V.x;
-    const float4 Gs = fold_slabs(G, i, sl);
-    const float* Gp = &Gs.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float gg = Gp[j] * gscale;
-      Mp[j] = b1 * Mp[j] + (1.f - b1) * gg;
-      Vp[j] = b2 * Vp[j] + (1.f - b2) * gg * gg;
-      const float mh = Mp[j] / bc1, vh = Vp[j] / bc2;
-      Wp[j] -= lr * (mh / (sqrtf(vh) + eps) + wd * Wp[j]);
-    }
-    reinterpret_cast<float4*>(w)[i] = W;
-    reinterpret_cast<float4*>(m)[i] = M;
-    reinterpret_cast<float4*>(v)[i] = V;
-    if (wb) reinterpret_cast<uint2*>(wb)[i] = make_uint2(pack_bf2(W.x, W.y), pack_bf2(W.z, W.w));
-    if (zero_g) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);  // next clock's accumulator
-  }
-}
-
-static AdamSlabs checked_slabs(const AdamSlabs* slabs, int64_t n, const char* what) {
-  AdamSlabs sl{};
-  if (slabs) {
-    sl = *slabs;
-    for (int k = 0; k < sl.n; ++k)
-      if ((sl.off[k] & 3) || (sl.len[k] & 3) || (sl.plane[k] & 3) || sl.off[k] < 0 || sl.len[k] < 0 ||
-          sl.len[k] > sl.plane[k] || sl.off[k] + sl.len[k] > n || sl.nsplit[k] < 1 ||
-          (reinterpret_cast<uintptr_t>(sl.p[k]) & 15))
-        throw std::runtime_error(std::string(what) + " slabs: 16-byte aligned planes and ranges inside the gradient");
-  }
-  if (sl.n < 0 || sl.n > 4) throw std::runtime_error(std::string(what) + " slabs: at most 4 regions");
-  return sl;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    adam_update4(w, m, v, g, i, sl, lr, b1, b2, eps, wd, bc1, bc2, gscale, wb, zero_g);
 }
 
 static void check_vec(const void* p, int64_t n, const char* what) {

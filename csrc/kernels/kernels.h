@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stdexcept>
+#include <string>
+
 namespace minips_k {
 
 typedef uint16_t bf16_t;
@@ -210,6 +213,22 @@ struct AdamSlabs {
   int64_t off[4] = {0, 0, 0, 0}, len[4] = {0, 0, 0, 0}, plane[4] = {0, 0, 0, 0};
   int nsplit[4] = {0, 0, 0, 0};
 };
+// The one host-side check of a slab list against a gradient of n elements, run by every launcher that
+// folds slabs (adam_apply, slab_pack, grad_sumsq, adam_clip_apply, ps_push_dense): what passes keeps
+// every plane read of slab_fold (dense_update.h) in range and 16-byte aligned. Null = no slabs.
+// (inline: minips_amd._optk links gradclip.hip alone)
+inline AdamSlabs checked_slabs(const AdamSlabs* slabs, int64_t n, const char* what) {
+  AdamSlabs sl{};
+  if (!slabs) return sl;
+  sl = *slabs;
+  if (sl.n < 0 || sl.n > 4) throw std::runtime_error(std::string(what) + " slabs: at most 4 regions");
+  for (int k = 0; k < sl.n; ++k)
+    if ((sl.off[k] & 3) || (sl.len[k] & 3) || (sl.plane[k] & 3) || sl.off[k] < 0 || sl.len[k] < 0 ||
+        sl.len[k] > sl.plane[k] || sl.off[k] + sl.len[k] > n || sl.nsplit[k] < 1 ||
+        (reinterpret_cast<uintptr_t>(sl.p[k]) & 15))
+      throw std::runtime_error(std::string(what) + " slabs: 16-byte aligned planes and ranges inside the gradient");
+  return sl;
+}
 // several ranks: out = g + the split-K planes of its regions, g cleared (the reduce-scatter input)
 void slab_pack(float* g, float* out, int64_t n, const AdamSlabs* slabs, hipStream_t s);
 void adam_apply(float* w, float* m, float* v, const float* g, int64_t n, float lr, float beta1, float beta2,

@@ -703,6 +703,31 @@ def wd_emb_backward(dX, dwide, inv, F, D, grad_rows, x_off=0, csr=None, sorted_r
 
 
 # ----------------------------------------------------------------------------- optimizers
+def _slab_args(slabs):
+    return [(s, int(n), int(p), int(o)) for s, n, p, o in slabs]
+
+
+def _fold_slabs(g, slabs, group4=True):
+    """g + its split-K planes ((slab, nsplit, plane, offset) each), an exact fp32 model of the kernels' fold
+    (slab_fold in csrc/kernels/dense_update.h); ``g`` itself when there are none. ``group4``: the order of what
+    an Adam consumes (adam_apply, adam_clip_apply, grad_sumsq) -- groups of four planes as (a0+a1)+(a2+a3),
+    then the remainder one by one. Otherwise plane by plane, the order of what is shipped (slab_pack, the
+    one-sided dense push). The two round differently from 4 planes on."""
+    if not slabs:
+        return g
+    x = g.clone()
+    for s, n, p, o in slabs:
+        P, r = s[: n * p].view(n, p), x[o: o + p]
+        z = 0
+        while group4 and z + 3 < n:
+            r += (P[z] + P[z + 1]) + (P[z + 2] + P[z + 3])
+            z += 4
+        while z < n:
+            r += P[z]
+            z += 1
+    return x
+
+
 def adam_apply(w, m, v, g, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, grad_scale=1.0,
                w_bf16=None, step_dev=None, zero_g=False, slabs=()):
     """Fused Adam(W). ``step_dev`` (int32 [1] device tensor): the bias-correction step is read on the
@@ -711,14 +736,9 @@ def adam_apply(w, m, v, g, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.
     ``slabs``: (slab, nsplit, plane, offset) split-K gradient planes folded into g[offset:offset+plane]."""
     if _gpu(w):
         kernels().adam_apply(w, m, v, g, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-                             int(step), float(grad_scale), w_bf16, step_dev, bool(zero_g),
-                             [(s, int(n), int(p), int(o)) for s, n, p, o in slabs])
+                             int(step), float(grad_scale), w_bf16, step_dev, bool(zero_g), _slab_args(slabs))
         return
-    g_in = g
-    if slabs:
-        g = g.clone()
-        for s, n, p, o in slabs:
-            g[o: o + p] += s[: n * p].view(n, p).sum(0)
+    g_in, g = g, _fold_slabs(g, slabs)
     if step_dev is not None:
         step = int(step_dev.reshape(-1)[0])
     gg = g * grad_scale
@@ -733,28 +753,6 @@ def adam_apply(w, m, v, g, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.
 
 
 # ----------------------------------------------------------------------------- global-norm clipping
-def _slab_args(slabs):
-    return [(s, int(n), int(p), int(o)) for s, n, p, o in slabs]
-
-
-def _fold_slabs(g, slabs):
-    """The fp32 gradient the Adam consumes: g + its split-K planes in the Adam kernel's order (groups of
-    four planes as (a0+a1)+(a2+a3), then the remainder one by one). ``g`` itself when there are none."""
-    if not slabs:
-        return g
-    x = g.clone()
-    for s, n, p, o in slabs:
-        P, r = s[: n * p].view(n, p), x[o: o + p]
-        z = 0
-        while z + 3 < n:
-            r += (P[z] + P[z + 1]) + (P[z + 2] + P[z + 3])
-            z += 4
-        while z < n:
-            r += P[z]
-            z += 1
-    return x
-
-
 def grad_sumsq(g, part, L=None, slabs=()):
     """part[0:L] (fp64) = partial sums of squares of the fp32 gradient ``g`` (+ ``slabs``, as adam_apply's),
     squared and accumulated in fp64: their sum is the squared l2 norm, non-finite exactly when an element is.
@@ -813,11 +811,9 @@ def slab_pack(g, out, slabs=()):
     """out = g + the split-K planes ``slabs`` ((slab, nsplit, plane, offset), as adam_apply) folded
     into their regions; g cleared -- a several-rank dense clock's reduce-scatter input in one pass."""
     if _gpu(g):
-        kernels().slab_pack(g, out, [(s, int(n), int(p), int(o)) for s, n, p, o in slabs])
+        kernels().slab_pack(g, out, _slab_args(slabs))
         return out
-    out.copy_(g)
-    for s, n, p, o in slabs:
-        out[o: o + p] += s[: n * p].view(n, p).sum(0)
+    out.copy_(_fold_slabs(g, slabs, group4=False))
     g.zero_()
     return out
 

@@ -368,6 +368,8 @@ class DenseTable:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pipe = _Pipeline(comm, consistency, staleness, kind="dense", w1=overlap_w1)
         self._pending = False
+        self._sink = None  # the split-K slab sink, once a model asked for one (slab_sink)
+        self._rs_send = None  # the reduce-scatter input the sink's planes are packed into, on first use
         # async clocks: a ring of staleness+2 gradient buffers, so the side stream reduces clock
         # t's gradients while the compute stream already writes clock t+1's.
         self._ring = [self.grad] + [torch.zeros_like(self.grad) for _ in range(self.pipe.staleness + 1)] \
@@ -415,11 +417,55 @@ class DenseTable:
             raise RuntimeError("lr_schedule inside a HIP-graph capture: the captured clock would replay one lr")
         return self.lr_schedule.lr(step, self.lr)
 
-    def _adam_clip(self, w, m, v, gs, step, out, sd, zero_g, slabs, write_stats=True):
-        """The clipping Adam on one piece, once the clock's partial sums are complete."""
-        ops.adam_clip_apply(w, m, v, gs, self.lr_at(step), self._clip_part, self.clip_norm, self._clip_stats,
-                            self.betas[0], self.betas[1], self.eps, self.weight_decay, step, w_bf16=out, step_dev=sd,
-                            zero_g=zero_g, slabs=slabs, write_stats=write_stats)
+    # -- the optimizer and the reduce-scatter of one piece (the flat shard or a bucket's slice) ---------
+    def _optimize(self, w, m, v, gs, out, step, sd, zero_g, slabs, part=None, write_stats=True) -> bool:
+        """The table's optimizer on one owned piece: gradient ``gs`` (+ split-K ``slabs``) into ``w`` (state
+        ``m`` / ``v``) and ``out``, the piece's slice of params (a bf16 pull is written by the kernel, any other
+        is copied from ``w``). True if ``gs`` was cleared on the way (Adam with ``zero_g``).
+
+        ``clip_norm`` takes two calls per piece, since the norm needs every piece and rank in between: with
+        ``part`` (the piece's slice of the partial sums) only ops.grad_sumsq is launched; the call without it,
+        once the caller has all-reduced the partial sums, is the clipping Adam."""
+        wb = out if self.pull_dtype == torch.bfloat16 else None
+        lr = self.lr if self.lr_schedule is None else self.lr_at(step)
+        hyper = (self.betas[0], self.betas[1], self.eps, self.weight_decay, step)
+        adam = self.optimizer == "adam"
+        if adam and part is not None:
+            ops.grad_sumsq(gs, part, slabs=slabs)
+            return False
+        if adam and self.clip_norm is not None:
+            ops.adam_clip_apply(w, m, v, gs, lr, self._clip_part, self.clip_norm, self._clip_stats, *hyper,
+                                w_bf16=wb, step_dev=sd, zero_g=zero_g, slabs=slabs, write_stats=write_stats)
+        elif adam:
+            ops.adam_apply(w, m, v, gs, lr, *hyper, 1.0, wb, step_dev=sd, zero_g=zero_g, slabs=slabs)
+        elif self.optimizer == "adagrad":
+            ops.adagrad_apply(w, m, gs, lr, self.eps, 1.0, wb)
+        elif self.optimizer == "sgd":
+            ops.sgd_apply(w, gs, lr, 1.0, wb)
+        elif self.optimizer == "add":  # the reference server apply: w += delta
+            w.add_(gs)
+            if wb is not None:
+                ops.cast_f32_bf16(w, wb)
+        else:
+            raise ValueError(self.optimizer)
+        if wb is None:
+            out.copy_(w)
+        return adam and zero_g
+
+    def _reduce_scatter(self, dst, g, lo: int = 0) -> bool:
+        """dst = this rank's slice of the sum over ranks of ``g``, elements [lo, lo + g.numel()) of the
+        gradient buffer. With a slab sink (several ranks) the split-K weight-gradient planes inside ``g`` are
+        folded into the reduce-scatter input and ``g`` is cleared, in one pass (ops.slab_pack: no split-K
+        reduce kernels, no fill); True then."""
+        if self._sink is None or self.comm.world == 1:
+            self.comm.reduce_scatter(dst, g)
+            return False
+        if self._rs_send is None:
+            self._rs_send = torch.empty_like(self.grad)
+        send = self._rs_send[lo: lo + g.numel()]
+        ops.slab_pack(g, send, self._sink.take(g))
+        self.comm.reduce_scatter(dst, send)
+        return True
 
     # -- bucketed clocks ----------------------------------------------------------------------
     def _init_buckets(self, starts):
@@ -496,50 +542,18 @@ class DenseTable:
         self._issued.add(k)
         g_b, gs_own, w, m, v, p_own, p_b = self._bucket_views(k, grad)
         local = comm.world == 1 and not comm.force  # one rank owns the whole bucket: no copy
-        packed = False
-        if local:
-            gs = g_b
-        else:
-            sink = getattr(self, "_sink", None)
-            if sink is not None and comm.world > 1:  # the bucket's split-K planes folded into its RS input
-                send = self.__dict__.get("_rs_send")
-                if send is None:
-                    send = self._rs_send = torch.empty_like(self.grad)
-                lo, hi = self.buckets[k]
-                ops.slab_pack(g_b, send[lo:hi], sink.take(g_b))
-                comm.reduce_scatter(gs_own, send[lo:hi])
-                packed = True
-            else:
-                comm.reduce_scatter(gs_own, g_b)
-            gs = gs_own
-        out = p_own if self.pull_dtype == torch.bfloat16 else None
-        zeroed = False
-        lr = self.lr if self.lr_schedule is None else self.lr_at(step)
-        if self.optimizer == "adam":
-            sink = getattr(self, "_sink", None)  # (one rank: the bucket's split-K wgrad planes)
-            slabs = sink.take(gs) if sink is not None and local else ()
-            if self.clip_norm is not None:
-                # the bucket's share of the norm now; its Adam and all-gather once the norm is whole
-                o, L = self._clip_sl[k]
-                ops.grad_sumsq(gs, self._clip_part[o: o + L], L, slabs)
-                self._clip_todo.append((k, gs, slabs, sd, local, packed))
-                return
-            ops.adam_apply(w, m, v, gs, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, step, 1.0,
-                           out, step_dev=sd, zero_g=local, slabs=slabs)
-            zeroed = local or packed  # the kernel (or the pack) cleared the gradient
-        elif self.optimizer == "adagrad":
-            ops.adagrad_apply(w, m, gs, lr, self.eps, 1.0, out)
-        elif self.optimizer == "sgd":
-            ops.sgd_apply(w, gs, lr, 1.0, out)
-        elif self.optimizer == "add":
-            w.add_(gs)
-            if out is not None:
-                ops.cast_f32_bf16(w, out)
-        else:
-            raise ValueError(self.optimizer)
-        if out is None:
-            p_own.copy_(w)
-        self._bucket_finish(k, g_b, p_b, p_own, zeroed or packed)
+        packed = not local and self._reduce_scatter(gs_own, g_b, self.buckets[k][0])
+        gs = g_b if local else gs_own
+        # (one rank: the bucket's split-K wgrad planes go to its Adam)
+        slabs = self._sink.take(gs) if self._sink is not None and local and self.optimizer == "adam" else ()
+        args = (w, m, v, gs, p_own, step, sd, local, slabs)
+        if self.clip_norm is not None:
+            # the bucket's share of the norm now; its Adam and all-gather once the norm is whole
+            o, L = self._clip_sl[k]
+            self._optimize(*args, part=self._clip_part[o: o + L])
+            self._clip_todo.append((k, args, packed))
+            return
+        self._bucket_finish(k, g_b, p_b, p_own, self._optimize(*args) or packed)
 
     def _bucket_finish(self, k, g_b, p_b, p_own, cleared):
         comm = self.comm
@@ -550,20 +564,16 @@ class DenseTable:
         bb = comm.stats.bucket_bytes
         bb[key] = bb.get(key, 0) + nb
 
-    def _clip_buckets(self, grad: torch.Tensor, step: int):
+    def _clip_buckets(self, grad: torch.Tensor):
         """The clipped clock's second half, once every bucket's partial sums are in: the one all-reduce
         of the partials, then Adam + all-gather per bucket in index order."""
         todo, self._clip_todo = sorted(self._clip_todo, key=lambda e: e[0]), []
         if not todo:
             return
         self.comm.all_reduce_(self._clip_part)
-        for i, (k, gs, slabs, sd, local, packed) in enumerate(todo):
-            g_b, _, w, m, v, p_own, p_b = self._bucket_views(k, grad)
-            out = p_own if self.pull_dtype == torch.bfloat16 else None
-            self._adam_clip(w, m, v, gs, step, out, sd, local, slabs, write_stats=i == 0)
-            if out is None:
-                p_own.copy_(w)
-            self._bucket_finish(k, g_b, p_b, p_own, local or packed)
+        for i, (k, args, packed) in enumerate(todo):
+            g_b, _, _, _, _, p_own, p_b = self._bucket_views(k, grad)
+            self._bucket_finish(k, g_b, p_b, p_own, self._optimize(*args, write_stats=i == 0) or packed)
 
     @traced("dense.bucket_ready")
     def bucket_ready(self, k: int, events=()):
@@ -666,7 +676,7 @@ class DenseTable:
                         if k not in self._issued:
                             self._bucket_work(k, grad, step)
                     if self.clip_norm is not None:
-                        self._clip_buckets(grad, step)
+                        self._clip_buckets(grad)
                 else:
                     self._step_dev_for_clock()
                 self._issued = set()
@@ -684,19 +694,7 @@ class DenseTable:
                     # Adam clears it in the same pass (one fewer full-size kernel per clock)
                     cleared = self._apply(grad, step, zero_g=grad.numel() == self.shard, step_dev=sd)
                 else:
-                    sink = getattr(self, "_sink", None)
-                    if sink is not None:
-                        # the split-K weight-gradient planes folded into the reduce-scatter input and
-                        # the gradient cleared, in one pass (no split-K reduce kernels, no fill)
-                        send = self.__dict__.get("_rs_send")
-                        if send is None:
-                            send = self._rs_send = torch.empty_like(grad)
-                        ops.slab_pack(grad, send, sink.take(grad))
-                        comm.reduce_scatter(self.grad_shard, send)
-                        cleared = True
-                    else:
-                        comm.reduce_scatter(self.grad_shard, grad)
-                        cleared = False
+                    cleared = self._reduce_scatter(self.grad_shard, grad)
                     self._apply(self.grad_shard, step, step_dev=sd)
                 comm.all_gather(self.params, self.params[self.base: self.base + self.shard])
             else:
@@ -723,40 +721,20 @@ class DenseTable:
             # (an asynchronous clock applies after the next step's GEMMs ran: those write the next
             # buffer of the gradient ring -- and its own planes -- which the ring's clock wait protects)
             return None
-        sink = getattr(self, "_sink", None)
-        if sink is None:
-            sink = self._sink = _SlabSink(self)
-        return sink
+        if self._sink is None:
+            self._sink = _SlabSink(self)
+        return self._sink
 
     def _apply(self, g: torch.Tensor, step: int, zero_g: bool = False, step_dev=None) -> bool:
         """Apply the optimizer to the owned shard; True if ``g`` was cleared on the way."""
-        out = self.params[self.base: self.base + self.shard] if self.pull_dtype == torch.bfloat16 else None
-        lr = self.lr if self.lr_schedule is None else self.lr_at(step)
-        if self.optimizer == "adam":
-            sink = getattr(self, "_sink", None)
-            slabs = sink.take(g) if sink is not None else ()  # (taken once: both kernels fold the same planes)
-            if self.clip_norm is None:
-                ops.adam_apply(self.master, self.m, self.v, g, lr, self.betas[0], self.betas[1], self.eps,
-                               self.weight_decay, step, 1.0, out, step_dev=step_dev, zero_g=zero_g, slabs=slabs)
-            else:
-                self.comm.all_reduce_(ops.grad_sumsq(g, self._clip_part, slabs=slabs))
-                self._adam_clip(self.master, self.m, self.v, g, step, out, step_dev, zero_g, slabs)
-            if out is None:
-                self.params[self.base: self.base + self.shard].copy_(self.master)
-            return zero_g
-        elif self.optimizer == "adagrad":
-            ops.adagrad_apply(self.master, self.m, g, lr, self.eps, 1.0, out)
-        elif self.optimizer == "sgd":
-            ops.sgd_apply(self.master, g, lr, 1.0, out)
-        elif self.optimizer == "add":  # the reference server apply: w += delta
-            self.master.add_(g)
-            if out is not None:
-                ops.cast_f32_bf16(self.master, out)
-        else:
-            raise ValueError(self.optimizer)
-        if out is None:
-            self.params[self.base: self.base + self.shard].copy_(self.master)
-        return False
+        # (taken once: with clip_norm both kernels fold the same planes)
+        slabs = self._sink.take(g) if self._sink is not None and self.optimizer == "adam" else ()
+        args = (self.master, self.m, self.v, g, self.params[self.base: self.base + self.shard], step, step_dev,
+                zero_g, slabs)
+        if self.clip_norm is not None:
+            self._optimize(*args, part=self._clip_part)
+            self.comm.all_reduce_(self._clip_part)
+        return self._optimize(*args)
 
     def hold(self, event):
         """A clock of this table was issued on another stream (WideDeep runs one rank's dense Adam

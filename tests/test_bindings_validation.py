@@ -367,6 +367,23 @@ def _(c):
                ("members", value(lambda d: torch.zeros(16, dtype=I32, device=d)))]
 
 
+def _bad_slabs(n):
+    """Slab lists the bindings refuse for a gradient of n elements (test_optk_validation.py's): each is refused
+    by the launcher's own check as well, so none could reach a kernel."""
+    h = n // 2
+
+    def mk(d, ns=3, plane=h, off=0):
+        return [(torch.zeros(ns * plane, device=d), ns, plane, off)]
+
+    return [("slabs", value(lambda d: mk(d, off=n - h + 4))),  # the region ends past the gradient
+            ("slabs", value(lambda d: mk(d, plane=h - 2))),  # plane: no multiple of 4
+            ("slabs", value(lambda d: mk(d, off=2))),  # offset: no multiple of 4
+            ("slabs", value(lambda d: mk(d, ns=0))),
+            # misaligned planes
+            ("slabs", value(lambda d: [(torch.zeros(3 * h + 8, device=d)[1: 1 + 3 * h], 3, h, 0)])),
+            ("slabs", value(lambda d: mk(d) * 5))]  # more than 4 regions
+
+
 @entry("adam_apply")
 def _(c):
     a = dict(w=c.t((16,), F32, 1), m=c.t((16,), F32), v=c.t((16,), F32), g=c.t((16,), F32, 1), lr=0.1, beta1=0.9,
@@ -378,14 +395,14 @@ def _(c):
                ("w_bf16", value(lambda d: torch.zeros(16, dtype=F32, device=d))),
                ("slabs", value(lambda d: [(torch.zeros(16, device=d)[:15], 1, 16, 0)])),
                ("slabs", value(lambda d: [(torch.zeros(16, dtype=F64, device=d), 1, 16, 0)])),
-               ("slabs", value(lambda d: [(torch.zeros(16, device=d), 1, 16, -4)]))]
+               ("slabs", value(lambda d: [(torch.zeros(16, device=d), 1, 16, -4)]))] + _bad_slabs(16)
 
 
 @entry("slab_pack")
 def _(c):
     a = dict(g=c.t((16,), F32, 1), out=c.t((16,), F32, 3), slabs=[])
     return a, [("g", wider), ("g", pinned), ("out", wider), ("out", short),
-               ("slabs", value(lambda d: [(torch.zeros(16, device=d)[:15], 1, 16, 0)]))]
+               ("slabs", value(lambda d: [(torch.zeros(16, device=d)[:15], 1, 16, 0)]))] + _bad_slabs(16)
 
 
 @entry("sgd_apply")
@@ -561,7 +578,7 @@ def _(c):
 def _(c):
     a = dict(grad=c.t((8,), F32, 1), inbox=_inbox(c), data_off=64, S=8, slabs=[])
     return a, [("grad", wider), ("grad", short), ("inbox", wider), ("inbox", pinned), ("S", value(-4)),
-               ("slabs", value(lambda d: [(torch.zeros(8, device=d)[:7], 1, 8, 0)]))]
+               ("slabs", value(lambda d: [(torch.zeros(8, device=d)[:7], 1, 8, 0)]))] + _bad_slabs(8)
 
 
 def _ps_gather(dtype):

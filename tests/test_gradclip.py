@@ -52,6 +52,40 @@ def test_grad_sumsq_cpu():
     assert float(part.sum()) == float(x.double().square().sum())
 
 
+def test_fold_slabs_models(monkeypatch):
+    """ops._fold_slabs is the one CPU model of the kernels' two plane-fold orders: plane by plane against a
+    plain loop, grouped against the written-out expression, and the CPU branches of slab_pack (plane by
+    plane) and adam_apply (grouped) route through it."""
+    gen = torch.Generator().manual_seed(7)
+    g = torch.randn(64, generator=gen)
+    planes = torch.randn(6, 16, generator=gen)
+    slabs = [(planes.reshape(-1), 6, 16, 32)]
+    loop = g.clone()
+    for z in range(6):
+        for e in range(16):
+            loop[32 + e] = loop[32 + e] + planes[z, e]
+    assert torch.equal(ops._fold_slabs(g, slabs, group4=False), loop)
+    grouped = g.clone()
+    grouped[32:48] = ((g[32:48] + ((planes[0] + planes[1]) + (planes[2] + planes[3]))) + planes[4]) + planes[5]
+    assert torch.equal(ops._fold_slabs(g, slabs), grouped)
+    assert not torch.equal(grouped, loop)  # the two orders differ on this input
+    assert ops._fold_slabs(g, ()) is g
+    calls = []
+    fold = ops._fold_slabs
+
+    def spy(g_, slabs_, group4=True):
+        calls.append(group4)
+        return fold(g_, slabs_, group4)
+
+    monkeypatch.setattr(ops, "_fold_slabs", spy)
+    src, out = g.clone(), torch.empty(64)
+    ops.slab_pack(src, out, slabs)
+    assert calls == [False] and torch.equal(out, loop) and int((src != 0).sum()) == 0
+    m, w = torch.zeros(64), torch.zeros(64)
+    ops.adam_apply(w, m, torch.zeros(64), g, 1e-3, beta1=0.0, slabs=slabs)
+    assert calls == [False, True] and torch.equal(m, grouped)  # beta1 = 0: m = 0 * m + 1 * g, exact
+
+
 def test_clip_scale_rule():
     assert ops.clip_scale(4.0, 10.0) == (2.0, 1.0, False)  # below the threshold: exactly 1
     norm, scale, skip = ops.clip_scale(1e60, 1.0)

@@ -1,6 +1,7 @@
 """Global-norm gradient clipping on the GPU (csrc/kernels/gradclip.hip through minips_amd._optk):
 grad_sumsq against the CPU fold summed in fp64, adam_clip_apply bit for bit against adam_apply at the
-scale it derived, the skip of a non-finite clock, and the clipped DenseTable / GPT-2 / graphed MLP
+scale it derived, the two plane-fold orders bit for bit against their CPU models, the skip of a non-finite
+clock, and the clipped DenseTable / GPT-2 / graphed MLP
 against their CPU or eager twins."""
 import math
 
@@ -67,6 +68,42 @@ def test_grad_sumsq(n, L, with_slabs, gradients, dev):
     print(f"grad_sumsq n={n} L={L} slabs={with_slabs}: rel err {abs(got - ref) / ref:.3e} (bound {tol:.1e})")
     assert abs(got - ref) <= tol * ref
     assert torch.equal(gd.cpu(), g)  # a read pass
+
+
+def _check_fold_orders(g, slabs, dev, must_differ):
+    """Both plane-fold orders of the dense clock, bit for bit against their CPU models (ops._fold_slabs):
+    slab_pack ships the planes added one by one, an Adam consumes them in groups of four."""
+    n = g.numel()
+    seq, grouped = ops._fold_slabs(g, slabs, group4=False), ops._fold_slabs(g, slabs)
+    differ = int((seq != grouped).sum())
+    print(f"fold orders n={n} nsplit={[s[1] for s in slabs]}: {differ} elements differ")
+    if must_differ:  # (not vacuous: this input tells the two orders apart)
+        assert differ > 0
+    ref_out, ref_src = torch.empty(n), g.clone()
+    ops.slab_pack(ref_src, ref_out, slabs)
+    assert torch.equal(ref_out, seq)
+    src, out = g.to(dev), torch.empty(n, device=dev)
+    ops.slab_pack(src, out, _to(slabs, dev))
+    assert torch.equal(out.cpu(), ref_out) and int((src != 0).sum()) == 0
+    # beta1 = 0 and m = 0: m = 0 * m + 1 * (g * 1) is the folded gradient itself, exactly
+    w, m, v = (torch.zeros(n, device=dev) for _ in range(3))
+    ops.adam_apply(w, m, v, g.to(dev), 1e-3, beta1=0.0, grad_scale=1.0, slabs=_to(slabs, dev))
+    assert torch.equal(m.cpu(), grouped)
+
+
+@pytest.mark.parametrize("nsplit", [3, 4, 5, 8, 16])
+def test_slab_fold_orders_are_pinned(nsplit, dev):
+    gen = torch.Generator().manual_seed(7)
+    g = torch.randn(64, generator=gen)
+    slabs = [(torch.randn(nsplit * 16, generator=gen), nsplit, 16, 32)]
+    _check_fold_orders(g, slabs, dev, must_differ=nsplit >= 5)
+
+
+def test_slab_fold_orders_are_pinned_across_workgroups(gradients, dev):
+    """The same at n = 4100 (several workgroups), regions of 1 / 3 / 5 / 8 planes at the start, in the
+    middle and at the end."""
+    g, slabs, _, _ = gradients[4100]
+    _check_fold_orders(g, slabs, dev, must_differ=True)
 
 
 def test_grad_sumsq_large_elements_stay_finite(dev):
