@@ -9,6 +9,8 @@
   small torch extension with the same rule -- a GPU tensor without it raises.
 * ``_optk``     -- the global-norm gradient-clipping kernels of the dense clock (fp64 partial sums of
   squares, the clipping Adam): a third small torch extension, same rule.
+* ``_ftrlk``    -- the FTRL-Proximal apply of sparse table rows (``SparseTable(optimizer="ftrl")``): a
+  fourth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -59,6 +61,11 @@ def optk():
     return _load("_optk", "gfx950 HIP gradient-clipping kernels")
 
 
+def ftrlk():
+    """Return the HIP FTRL-Proximal kernel module or raise a loud error."""
+    return _load("_ftrlk", "gfx950 HIP FTRL-Proximal kernel")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -74,6 +81,10 @@ def evalk_available() -> bool:
 
 def optk_available() -> bool:
     return _available(optk)
+
+
+def ftrlk_available() -> bool:
+    return _available(ftrlk)
 
 
 def native_dir() -> str:

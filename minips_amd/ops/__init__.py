@@ -1,8 +1,8 @@
 """Data-plane ops of minips_amd.
 
 Every op has ONE device implementation: GPU tensors go to the hand-written gfx950 HIP
-kernels in ``minips_amd._kernels`` (the evaluation and gradient-clipping ops: in the small
-extensions ``_evalk`` / ``_optk``) and raise if that extension is missing -- there is no
+kernels in ``minips_amd._kernels`` (the evaluation, gradient-clipping and FTRL ops: in the small
+extensions ``_evalk`` / ``_optk`` / ``_ftrlk``) and raise if that extension is missing -- there is no
 silent eager fallback on a GPU. CPU tensors run a plain PyTorch reference of the same math;
 that path exists for the CPU/gloo plumbing configuration (BASELINE config 1) and as the fp32
 oracle the GPU numerics tests compare against.
@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import evalk, kernels, optk
+from .._native import evalk, ftrlk, kernels, optk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -510,6 +510,62 @@ def sparse_sgd(table, keys, base, grads, scale, n_dev=None):
         keys, grads = keys[:n], grads[:n]
     table.index_add_(0, keys - base, scale * grads, alpha=1.0) if grads.shape[1] == table.shape[1] else \
         table[:, : grads.shape[1]].index_add_(0, keys - base, scale * grads)
+
+
+def _sqrt_f32(x):
+    """The correctly rounded fp32 square root (the kernel's sqrtf): through fp64, whose 53 bits make the
+    second rounding exact. torch's vectorised fp32 sqrt on the CPU is off by one ulp on about 0.6 % of
+    inputs, which would show in z after the rule's division by alpha."""
+    return x.double().sqrt().to(torch.float32)
+
+
+def ftrl_weights(z, n, alpha, beta=1.0, l1=0.0, l2=0.0):
+    """The closed form w = f(z, n) of FTRL-Proximal in fp32, the rule's own operation order:
+    w = |z| <= l1 ? 0 : -(z - sign(z) * l1) / ((beta + sqrt(n)) / alpha + l2)."""
+    f = lambda v: torch.tensor(float(v), dtype=torch.float32, device=z.device)  # noqa: E731
+    shrunk = z - torch.sign(z) * f(l1)
+    scale = (f(beta) + _sqrt_f32(n)) / f(alpha) + f(l2)
+    return torch.where(z.abs() <= f(l1), torch.zeros_like(z), -shrunk / scale)
+
+
+def sparse_ftrl(table, zn, keys, base, grads, alpha, beta=1.0, l1=0.0, l2=0.0, n_dev=None, oor=None, blocks=0):
+    """Per-coordinate FTRL-Proximal (McMahan et al. 2013, Algorithm 1) on table rows keys - base, in fp32:
+        g2 = g * g;  n' = n + g2;  s' = sqrt(n');  s = sqrt(n);  den = alpha * (s' + s)
+        sigma = den > 0 ? g2 / den : 0;  z' = z + (g - sigma * w)
+        w' = |z'| <= l1 ? 0 : -(z' - sign(z') * l1) / ((beta + s') / alpha + l2)
+    ``zn`` [rows, 2W]: z in columns [0, W), n in [W, 2W) of the table's row. ``keys`` distinct; ``n_dev``
+    (device int64) bounds the prefix without a host sync; a key whose row is outside [0, rows) is skipped
+    and counted into ``oor`` (int64 [1]). ``blocks`` > 0 forces the GPU grid size. The CPU path is the
+    reference of the same operation sequence (g * g its own rounded product)."""
+    alpha, beta, l1, l2 = float(alpha), float(beta), float(l1), float(l2)
+    if _gpu(table):
+        ftrlk().sparse_ftrl(table, zn, keys, int(base), grads, alpha, beta, l1, l2, n_dev, oor, int(blocks))
+        return
+    if not alpha > 0 or not (beta >= 0 and l1 >= 0 and l2 >= 0):
+        raise RuntimeError(f"sparse_ftrl: alpha {alpha} must be positive, beta {beta}, l1 {l1}, l2 {l2} non-negative")
+    W, nrows = grads.shape[1], table.shape[0]
+    if table.dtype != torch.float32 or zn.dtype != torch.float32 or tuple(zn.shape) != (nrows, 2 * W):
+        raise RuntimeError(f"sparse_ftrl: fp32 table and zn [{nrows}, {2 * W}] expected, got {table.dtype} / "
+                           f"{zn.dtype} {tuple(zn.shape)}")
+    n = keys.numel()
+    if n_dev is not None:
+        n = min(n, int(n_dev.reshape(-1)[0]))
+    rows, g = keys[:n] - base, grads[:n].float()
+    ok = (rows >= 0) & (rows < nrows)
+    if oor is not None:
+        oor += int((~ok).sum())
+    rows, g = rows[ok], g[ok]
+    f = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    w, z, nn = table[rows, :W], zn[rows, :W], zn[rows, W:]
+    g2 = g * g
+    n1 = nn + g2
+    s1, s0 = _sqrt_f32(n1), _sqrt_f32(nn)
+    den = f(alpha) * (s1 + s0)
+    sigma = torch.where(den > 0, g2 / den, torch.zeros_like(den))
+    z1 = z + (g - sigma * w)
+    table[rows, :W] = ftrl_weights(z1, n1, alpha, beta, l1, l2)
+    zn[rows, :W] = z1
+    zn[rows, W:] = n1
 
 
 def embedding_bag_fwd(rows, idx, offsets, mean=False, out=None):

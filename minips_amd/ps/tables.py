@@ -908,13 +908,18 @@ class SparseTable:
     _local_apply = True  # this rank applies its pushes itself (the one-sided tables' owners apply)
     # hash tables need exact host counts (insert-on-miss must not see padding keys)
     _exact_counts = False
+    ftrl_zn = None  # FTRL-Proximal state [rows, 2 * width] (z | n), optimizer "ftrl" only
 
     def __init__(self, comm: Comm, num_rows: int, width: int, optimizer: str = "rowwise_adagrad",
                  lr: float = 0.01, eps: float = 1e-8, pull_dtype=torch.bfloat16, consistency: str = "bsp",
                  staleness: int = 0, split: int | None = None, table_id: int = 0, init_std: float = 0.01,
                  seed: int = 1234, p2p: bool | None = None, push_dtype=None, route: str = "mix",
-                 value_dtype=torch.float32, columns=None):
-        """``value_dtype`` float64: the reference's double tables (CreateTable<double>,
+                 value_dtype=torch.float32, columns=None, ftrl_beta: float = 1.0, l1: float = 0.0, l2: float = 0.0):
+        """``optimizer`` "ftrl": per-coordinate FTRL-Proximal (ops.sparse_ftrl states the rule) with ``lr`` as
+        its alpha, ``ftrl_beta``, ``l1`` and ``l2``; fp32 rows without ``split`` only. Its state is
+        ``ftrl_zn`` [rows, 2 * width] (z | n per row); ``nnz()`` counts the non-zero weights.
+
+        ``value_dtype`` float64: the reference's double tables (CreateTable<double>,
         lr_example.cpp:182; values read as double, kv_client_table.hpp:96-101) -- optimizer "add"
         (VectorStorage::SubAdd), rows pulled and pushed in fp64 (f64.hip kernels).
 
@@ -927,6 +932,14 @@ class SparseTable:
         (bf16rows.hip); rows of 16 / 32 / 64 values."""
         if value_dtype not in (torch.float32, torch.float64, torch.bfloat16):
             raise ValueError(f"value_dtype {value_dtype}")
+        if optimizer == "ftrl":
+            if value_dtype != torch.float32:
+                raise ValueError(f"optimizer 'ftrl' keeps fp32 rows, not {value_dtype}")
+            if split is not None:
+                raise ValueError("optimizer 'ftrl' has no split rows (one rule for every column)")
+            if not lr > 0 or ftrl_beta < 0 or l1 < 0 or l2 < 0:
+                raise ValueError(f"optimizer 'ftrl': lr (alpha) {lr} must be positive, ftrl_beta {ftrl_beta}, "
+                                 f"l1 {l1} and l2 {l2} non-negative")
         if value_dtype == torch.float64:
             if optimizer != "add":
                 raise ValueError("fp64 sparse tables support the reference's plain add apply only")
@@ -978,6 +991,9 @@ class SparseTable:
         self.state = torch.zeros(self._rows_alloc, dtype=torch.float32, device=dev) \
             if optimizer == "rowwise_adagrad" else None
         self.state2 = torch.zeros_like(self.state) if (self.state is not None and split is not None) else None
+        self.ftrl_beta, self.l1, self.l2 = float(ftrl_beta), float(l1), float(l2)
+        if optimizer == "ftrl":
+            self.ftrl_zn = torch.zeros(self._rows_alloc, 2 * width, dtype=torch.float32, device=dev)
         self._init_comm(consistency, staleness, p2p)
 
     def _init_comm(self, consistency, staleness, p2p):
@@ -1426,12 +1442,25 @@ class SparseTable:
             ops.sparse_sgd(self.shard, keys, base, g.contiguous(), -self.lr, n_dev=n_dev)
         elif self.optimizer == "add":
             ops.sparse_sgd(self.shard, keys, base, g.contiguous(), 1.0, n_dev=n_dev)
+        elif self.optimizer == "ftrl":
+            # a row outside the shard is skipped and counted; the count is read with the planner's, at drain
+            ops.sparse_ftrl(self.shard, self.ftrl_zn, keys, base, g.contiguous(), self.lr, self.ftrl_beta, self.l1,
+                            self.l2, n_dev=n_dev, oor=self._oor_counter())
         else:
             raise ValueError(self.optimizer)
 
     def drain(self):
         self.pipe.drain()
         self._check_keys()
+
+    def nnz(self) -> int:
+        """Non-zero weights of the whole table (every rank's owned rows, one all-reduce). Drains the
+        table and reads the count on the host: for report time, not the step."""
+        self.drain()
+        c = torch.count_nonzero(self.shard[: self.rows_local]).to(torch.int64).reshape(1)
+        if self.comm.world > 1:
+            self.comm.all_reduce_(c)
+        return int(c.item())
 
     def reset_after_rollback(self):
         self.pipe.reset()
@@ -1445,6 +1474,8 @@ class SparseTable:
             arrays["state"] = self.state
         if self.state2 is not None:
             arrays["state2"] = self.state2
+        if self.ftrl_zn is not None:
+            arrays["ftrl_zn"] = self.ftrl_zn
         meta = dict(global_rows=self.num_rows, base=self.base, rows=self.rows_local, cols=self.width,
                     clock=self.pipe.clock, table_id=self.table_id, rank=self.comm.rank, world=self.comm.world,
                     kind="sparse")
@@ -1467,6 +1498,8 @@ class SparseTable:
             out["state"] = self.state.view(-1, 1)
         if self.state2 is not None:
             out["state2"] = self.state2.view(-1, 1)
+        if self.ftrl_zn is not None:
+            out["ftrl_zn"] = self.ftrl_zn
         return out
 
     def finish_restore(self, clock: int):
@@ -1514,6 +1547,8 @@ class HashSparseTable(SparseTable):
         self.push_dtype = push_dtype or torch.float32  # MapStorage values are exact sums: keep fp32
         self.num_rows = MASK63
         self.width = width
+        if optimizer == "ftrl":
+            raise ValueError("optimizer 'ftrl' is not available on hash tables (SparseTable only)")
         self.optimizer, self.lr, self.eps = optimizer, lr, eps
         self.pull_dtype = pull_dtype
         self.split = None

@@ -110,7 +110,23 @@ def parse(argv=None):
     ap.add_argument("--lr_decay_steps", type=int, default=0,
                     help="> 0: cosine lr decay from the end of the warmup down to --lr_min_ratio at this step")
     ap.add_argument("--lr_min_ratio", type=float, default=0.0, help="final lr / peak lr of the cosine decay")
+    ap.add_argument("--sparse_optimizer", default="add", choices=["add", "ftrl"],
+                    help="LR server apply: add (the reference's w += delta) or ftrl (per-coordinate FTRL-Proximal "
+                         "with L1 / L2; Vector storage, float32)")
+    ap.add_argument("--ftrl_alpha", type=float, default=0.1, help="FTRL-Proximal per-coordinate rate alpha")
+    ap.add_argument("--ftrl_beta", type=float, default=1.0)
+    ap.add_argument("--ftrl_l1", type=float, default=0.0, help="L1 strength: weights with |z| <= l1 are exactly 0")
+    ap.add_argument("--ftrl_l2", type=float, default=0.0)
     args = ap.parse_args(argv)
+    if args.sparse_optimizer == "ftrl":
+        if args.model != "lr":
+            ap.error(f"--sparse_optimizer ftrl supports --model lr, not {args.model}")
+        if args.kStorageType != "vector":
+            ap.error("--sparse_optimizer ftrl needs --kStorageType Vector (no ftrl on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--sparse_optimizer ftrl keeps float32 weights, not --value_dtype {args.value_dtype}")
+        if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
+            ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     args.opt_flags = bool(args.clip_norm or args.lr_warmup or args.lr_decay_steps or args.lr_min_ratio)
     if args.opt_flags and args.model not in ("gpt2", "mlp"):
         ap.error(f"--clip_norm / --lr_warmup / --lr_decay_steps / --lr_min_ratio support --model gpt2 and mlp, "
@@ -131,6 +147,14 @@ def parse(argv=None):
         ap.error("--eval_every: held-out evaluation needs --transport collective (evaluate() is not implemented "
                  "on the onesided transport)")
     return args
+
+
+def _ftrl_kw(args) -> dict:
+    """SparseLRConfig fields of --sparse_optimizer ftrl (none without the flag)."""
+    if args.sparse_optimizer != "ftrl":
+        return {}
+    return dict(optimizer="ftrl", ftrl_alpha=args.ftrl_alpha, ftrl_beta=args.ftrl_beta, l1=args.ftrl_l1,
+                l2=args.ftrl_l2)
 
 
 def _load_input(args, comm):
@@ -229,7 +253,7 @@ def build(args, comm):
             nd = int(t.item())
         m = SparseLR(SparseLRConfig(num_dims=nd, alpha=args.alpha, consistency=args.consistency,
                                     staleness=args.staleness, storage=args.kStorageType,
-                                    value_dtype=getattr(torch, args.value_dtype)), comm)
+                                    value_dtype=getattr(torch, args.value_dtype), **_ftrl_kw(args)), comm)
         B = args.batch or 1024
         W = max(1, args.num_workers_per_node)
         return m, {0: m.table}, (lambda: _Skippable(_WorkerGroup([_Batches(shard, B, seed + _WSEED * w)
@@ -242,7 +266,7 @@ def build(args, comm):
         nd = args.num_dims or (5000 if args.small else 16_609_143)
         m = SparseLR(SparseLRConfig(num_dims=nd, alpha=args.alpha, consistency=args.consistency,
                                     staleness=args.staleness, storage=args.kStorageType,
-                                    value_dtype=getattr(torch, args.value_dtype)), comm)
+                                    value_dtype=getattr(torch, args.value_dtype), **_ftrl_kw(args)), comm)
         B = args.batch or (128 if args.small else 65536)
         W = max(1, args.num_workers_per_node)
         return m, {0: m.table}, \
@@ -702,6 +726,9 @@ def main(argv=None):
         torch.cuda.synchronize(comm.device)
     if hb:
         hb.stop()
+    ftrl_final = {}
+    if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
+        ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
     clip_final = {}
     if args.clip_norm:
         cs = tables[0].clip_stats()
@@ -712,7 +739,7 @@ def main(argv=None):
                               total_ms=round((time.perf_counter() - t_start) * 1e3, 1),
                               steady_ms_per_iter=round(steady_ms, 4) if steady_ms is not None else None,
                               world=comm.world, generation=generation,
-                              **({"evals": evals} if args.eval_every > 0 else {}), **clip_final)),
+                              **({"evals": evals} if args.eval_every > 0 else {}), **clip_final, **ftrl_final)),
               flush=True)
     if comm.world > 1:
         comm.barrier()

@@ -11,6 +11,8 @@
     python tools/bench_kernels.py nn    GPT-2 memory-bound kernels (LayerNorm, add, softmax-xent): TB/s
     python tools/bench_kernels.py emb   W&D embedding backward on a real Criteo-shaped plan
     python tools/bench_kernels.py plan  key planning: per-column sort vs hash dedupe + CSR
+    python tools/bench_kernels.py ftrl  FTRL-Proximal sparse apply vs sparse_sgd (W = 1, the LR step's keys)
+                                        and vs the row-wise Adagrad (W = 64): us and achieved GB/s
     torchrun --nproc-per-node N tools/bench_kernels.py rccl [--min-mb 0.25 --max-mb 256]
                                         RCCL bytes vs time per collective of the PS data plane
                                         (reduce-scatter, all-gather, all-to-all, all-to-all-v),
@@ -548,6 +550,49 @@ def cmd_issue(a):
     dist.destroy_process_group()
 
 
+def cmd_ftrl(a):
+    """sparse_ftrl against the existing applies on the same key sets, interleaved in one process. Bytes per
+    key: w read + write, zn read + write (FTRL), the Adagrad's row state read + write, g and the key read."""
+    from minips_amd.data.synthetic import SparseLRSynth
+
+    d = dev()
+    gen = torch.Generator(device=d).manual_seed(0)
+    lr_keys = torch.unique(SparseLRSynth(65536, nnz=64, device=d, seed=0).next()[1])
+    wide_keys = torch.randperm(4_000_000, device=d, generator=gen)[:400_000]
+    sets = (("lr step keys", lr_keys, 16_609_143, 1), ("400k of 4M rows", wide_keys, 4_000_000, 64))
+    for name, keys, rows, W in sets:
+        n = keys.numel()
+        g = torch.randn(n, W, device=d, generator=gen) * 0.1
+        # the same bits as the CPU reference? a prefix of the keys on copies of their rows
+        m = min(n, 8192)
+        tw, tzn = torch.randn(rows, W, device=d, generator=gen), torch.zeros(rows, 2 * W, device=d)
+        tzn[:, W:].uniform_(0, 4, generator=gen)
+        sub = torch.unique(keys[:m])
+        cw, czn = tw[sub].cpu(), tzn[sub].cpu()
+        ops.sparse_ftrl(cw, czn, torch.arange(sub.numel()), 0, g[: sub.numel()].cpu(), 0.1, 1.0, 1.0, 0.01)
+        ops.sparse_ftrl(tw, tzn, sub, 0, g[: sub.numel()], 0.1, 1.0, 1.0, 0.01)
+        diff = sum(int((x.cpu().view(torch.int32) != y.view(torch.int32)).sum())
+                   for x, y in ((tw[sub], cw), (tzn[sub], czn)))
+        print(f"ftrl {name}: W {W}, {n} keys over {rows} rows; {diff} of {3 * sub.numel() * W} elements of a "
+              f"{sub.numel()}-key apply differ bitwise from the CPU reference", flush=True)
+        state = torch.zeros(rows, device=d)
+        fns = {"sparse_ftrl": lambda: ops.sparse_ftrl(tw, tzn, keys, 0, g, 0.1, 1.0, 1.0, 0.01)}
+        if W == 1:
+            fns["sparse_sgd"] = lambda: ops.sparse_sgd(tw, keys, 0, g, -1e-6)
+            ybytes = n * (8 + 4 + 8)
+        else:
+            fns["sparse_rowwise_adagrad"] = lambda: ops.sparse_rowwise_adagrad(tw, state, keys, 0, g, 1e-6)
+            ybytes = n * (3 * 4 * W + 8 + 8)
+        nbytes = {"sparse_ftrl": n * (7 * 4 * W + 8)}
+        for k in fns:
+            nbytes.setdefault(k, ybytes)
+        for rnd in range(3):
+            us = median_rounds(fns, rounds=10, per=3)
+            cols = "   ".join(f"{k} {us[k]:9.1f} us {nbytes[k] / us[k] * 1e-3:8.1f} GB/s" for k in fns)
+            print(f"  round {rnd}: {cols}", flush=True)
+        del tw, tzn, state
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -575,6 +620,7 @@ def main(argv=None):
     p.add_argument("--T", type=int, default=1024)
     p.add_argument("--H", type=int, default=12)
     sub.add_parser("nn")
+    sub.add_parser("ftrl")
     for name in ("emb", "plan", "embstep"):
         sub.add_parser(name).add_argument("--batch", type=int, default=16384)
     p = sub.add_parser("rccl")

@@ -97,10 +97,16 @@ def build(args, comm):
 
         B = args.batch or 65536
         vdt = getattr(torch, args.value_dtype)
-        m = SparseLR(SparseLRConfig(consistency=args.consistency, staleness=args.staleness, value_dtype=vdt), comm)
+        ftrl = {}
+        if args.sparse_optimizer == "ftrl":
+            ftrl = dict(optimizer="ftrl", ftrl_alpha=args.ftrl_alpha, ftrl_beta=args.ftrl_beta, l1=args.ftrl_l1,
+                        l2=args.ftrl_l2)
+        m = SparseLR(SparseLRConfig(consistency=args.consistency, staleness=args.staleness, value_dtype=vdt, **ftrl),
+                     comm)
         data = SparseLRSynth(B, nnz=64, device=dev, seed=r)
+        extra = dict(sparse_optimizer="ftrl", ftrl=ftrl) if ftrl else {}
         return m, (lambda: m.train_step(*data.next())), B, "samples/s", \
-            dict(model=f"sparse LR, 16.6M features, 64 nnz/row, {args.value_dtype} table", seq_len=None)
+            dict(model=f"sparse LR, 16.6M features, 64 nnz/row, {args.value_dtype} table", seq_len=None, **extra)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -173,7 +179,15 @@ def main():
                     help="lr: table precision (float64 = the reference's CreateTable<double>)")
     ap.add_argument("--clip-norm", "--clip_norm", dest="clip_norm", type=float, default=0.0,
                     help="gpt2: > 0 clips the gradient to this global l2 norm in every clock (0: off)")
+    ap.add_argument("--sparse_optimizer", "--sparse-optimizer", dest="sparse_optimizer", default="add",
+                    choices=["add", "ftrl"], help="lr: the table's apply (ftrl: FTRL-Proximal; the result gains nnz)")
+    ap.add_argument("--ftrl_alpha", type=float, default=0.1)
+    ap.add_argument("--ftrl_beta", type=float, default=1.0)
+    ap.add_argument("--ftrl_l1", type=float, default=0.0)
+    ap.add_argument("--ftrl_l2", type=float, default=0.0)
     args = ap.parse_args()
+    if args.sparse_optimizer == "ftrl" and (args.model != "lr" or args.value_dtype != "float32"):
+        ap.error("--sparse_optimizer ftrl: --model lr with --value-dtype float32 only")
     if args.clip_norm and args.model != "gpt2":
         ap.error("--clip_norm: --model gpt2 only")
     if args.transport == "auto" and not args.model.startswith("dlrm"):
@@ -200,6 +214,8 @@ def main():
     if comm.world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     el = float(t)
+    if args.sparse_optimizer == "ftrl":  # after the timed window: a host read (collective)
+        cfg["nnz"] = model.nnz()
     if comm.rank == 0:
         print(json.dumps({
             "metric": f"{unit.split('/')[0]}/sec (whole job) {args.model} {cfg.pop('consistency', args.consistency)}",

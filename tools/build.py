@@ -13,6 +13,8 @@ Targets
             small torch extension that links k_evalmetrics.o only)
   optim_py  csrc/bindings/optim_py.cpp   -> minips_amd/_optk*.so      (global-norm gradient clipping: a third
             small torch extension, over k_gradclip.o only)
+  ftrl_py   csrc/bindings/ftrl_py.cpp    -> minips_amd/_ftrlk*.so     (the FTRL-Proximal sparse apply: a fourth
+            small torch extension, over k_ftrl.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -226,6 +228,11 @@ def build_optim_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "optim_py", "_optk", "k_gradclip.o")
 
 
+def build_ftrl_py(kobjs: list[str]) -> str:
+    """minips_amd/_ftrlk: the FTRL-Proximal binding over k_ftrl.o alone."""
+    return _build_small_ext(kobjs, "ftrl_py", "_ftrlk", "k_ftrl.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -252,7 +259,8 @@ def build_sanitized(kind: str) -> list[str]:
 
 
 def main(argv: list[str]) -> int:
-    targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py"}
+    targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
+                                  "ftrl_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -268,7 +276,7 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py", "eval_py", "optim_py"}:
+    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -277,6 +285,8 @@ def main(argv: list[str]) -> int:
             print("built", build_eval_py(kobjs))
         if targets & {"kernels", "optim_py"}:
             print("built", build_optim_py(kobjs))
+        if targets & {"kernels", "ftrl_py"}:
+            print("built", build_ftrl_py(kobjs))
     return 0
 
 
