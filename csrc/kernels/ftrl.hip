@@ -11,16 +11,13 @@
 
 #include "common.h"
 #include "ftrl.h"
+#include "ftrl_rule.h"
 
 namespace minips_k {
 
 namespace {
 
 constexpr int kBlock = 256;
-
-struct FtrlHyper {
-  float alpha, beta, l1, l2;
-};
 
 __device__ __forceinline__ int64_t count_of(int64_t n, const int64_t* n_dev) { return n_dev ? min(n, *n_dev) : n; }
 
@@ -30,29 +27,6 @@ __device__ __forceinline__ int64_t checked_row(int64_t key, int64_t base, int64_
   if ((uint64_t)row < (uint64_t)rows) return row;
   if (oor && first) atomicAdd(reinterpret_cast<unsigned long long*>(oor), 1ull);
   return -1;
-}
-
-// one coordinate of the rule: every operation is rounded on its own (the CPU reference's sequence)
-__device__ __forceinline__ void ftrl_coord(float& w, float& z, float& n, float g, const FtrlHyper h) {
-#pragma clang fp contract(off)
-  const float g2 = g * g;
-  const float n1 = n + g2;
-  const float s1 = sqrtf(n1), s0 = sqrtf(n);
-  const float den = h.alpha * (s1 + s0);
-  const float sigma = den > 0.f ? g2 / den : 0.f;
-  const float z1 = z + (g - sigma * w);
-  const float shrunk = z1 - copysignf(h.l1, z1);
-  const float scale = (h.beta + s1) / h.alpha + h.l2;
-  w = fabsf(z1) <= h.l1 ? 0.f : -shrunk / scale;
-  z = z1;
-  n = n1;
-}
-
-__device__ __forceinline__ void ftrl_coord4(float4& w, float4& z, float4& n, const float4 g, const FtrlHyper h) {
-  ftrl_coord(w.x, z.x, n.x, g.x, h);
-  ftrl_coord(w.y, z.y, n.y, g.y, h);
-  ftrl_coord(w.z, z.z, n.z, g.z, h);
-  ftrl_coord(w.w, z.w, n.w, g.w, h);
 }
 
 __global__ __launch_bounds__(kBlock) void ftrl_w1_kernel(float* table, int64_t ld, float* zn, int64_t rows,

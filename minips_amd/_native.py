@@ -11,6 +11,9 @@
   squares, the clipping Adam): a third small torch extension, same rule.
 * ``_ftrlk``    -- the FTRL-Proximal apply of sparse table rows (``SparseTable(optimizer="ftrl")``): a
   fourth small torch extension, same rule.
+* ``_wdftrlk``  -- the split-row apply with two rules, row-wise Adagrad on the deep columns and FTRL-Proximal
+  on the wide ones (``SparseTable(split=..., wide_optimizer="ftrl")``): a fifth small torch extension, same
+  rule.
 """
 from __future__ import annotations
 
@@ -66,6 +69,11 @@ def ftrlk():
     return _load("_ftrlk", "gfx950 HIP FTRL-Proximal kernel")
 
 
+def wdftrlk():
+    """Return the HIP Adagrad + FTRL-Proximal split-row kernel module or raise a loud error."""
+    return _load("_wdftrlk", "gfx950 HIP Adagrad + FTRL-Proximal split-row kernel")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -85,6 +93,10 @@ def optk_available() -> bool:
 
 def ftrlk_available() -> bool:
     return _available(ftrlk)
+
+
+def wdftrlk_available() -> bool:
+    return _available(wdftrlk)
 
 
 def native_dir() -> str:

@@ -60,12 +60,28 @@ class WideDeepConfig:
     # and no worse with modelled xGMI wire time either (ring RS/AG 0.498 vs 0.505, direct 0.487 vs
     # 0.517 ms/step, 8 emulated ranks; profiles/r6/ab_buckets_wire.txt)
     bucket_mb: float = 0.0
+    # the wide column's rule. "adagrad" (default): the row's second row-wise Adagrad accumulator. "ftrl":
+    # FTRL-Proximal with L1 / L2 on the columns >= emb_dim (SparseTable(wide_optimizer="ftrl")), the paper's
+    # recipe -- wide_l1 > 0 drives wide weights to exact zero. wide_grad_scale multiplies the pushed (mean-loss)
+    # gradient of those columns: batch size x world gives the summed-loss gradient that alpha 0.1, beta 1,
+    # l1 about 1 assume. Collective transport only.
+    wide_optimizer: str = "adagrad"
+    wide_alpha: float = 0.1
+    wide_beta: float = 1.0
+    wide_l1: float = 0.0
+    wide_l2: float = 0.0
+    wide_grad_scale: float = 1.0
 
     def __post_init__(self):
         if self.transport == "auto":
             self.transport = "onesided" if self.consistency in ("ssp", "asp") else "collective"
         if self.dense_transport is None:
             self.dense_transport = self.transport
+        if self.wide_optimizer not in ("adagrad", "ftrl"):
+            raise ValueError(f"wide_optimizer {self.wide_optimizer!r}: adagrad | ftrl")
+        if self.wide_optimizer == "ftrl" and self.transport == "onesided":
+            raise ValueError("wide_optimizer 'ftrl' needs transport 'collective' (the one-sided owners apply the "
+                             "row-wise Adagrad only)")
 
     @property
     def F(self):
@@ -177,7 +193,10 @@ class WideDeep(LookaheadPlans):
         self.emb = make("sparse", num_rows=self.num_rows, width=cfg.row_width, optimizer="rowwise_adagrad",
                         lr=cfg.lr_sparse, model=cfg.consistency, staleness=cfg.staleness, transport=cfg.transport,
                         split=D, init_std=0.01, seed=cfg.seed, columns=(bases, cfg.cards), pull_dtype=torch.bfloat16,
-                        **({"max_keys": cfg.max_batch * F} if onesided else {}))
+                        **({"max_keys": cfg.max_batch * F} if onesided else {}),
+                        **(dict(wide_optimizer="ftrl", wide_lr=cfg.wide_alpha, ftrl_beta=cfg.wide_beta, l1=cfg.wide_l1,
+                                l2=cfg.wide_l2, ftrl_grad_scale=cfg.wide_grad_scale)
+                           if cfg.wide_optimizer == "ftrl" else {}))
         # wide weights start at zero (columns >= D)
         self.emb.shard[:, D:].zero_()
         # Dense layout: layer 1 is stored as W_ext [n_out, k_pad] with the bias in column k_in; its
@@ -509,6 +528,11 @@ class WideDeep(LookaheadPlans):
         if k is not None and all(b is None or b >= k for b in self._wbucket[layer:]):
             for j in sorted({b for b in self._wbucket[layer:] if b is not None}, reverse=True):
                 self.dense.bucket_ready(j, events=(side.mark(),))
+
+    def wide_nnz(self) -> int:
+        """Non-zero wide weights of the whole table (SparseTable.wide_nnz: drains, one all-reduce)."""
+        self.drain()
+        return self.emb.wide_nnz()
 
     def drain(self):
         pend_side = self.__dict__.pop("_side_pending", None)

@@ -1,8 +1,8 @@
 """Data-plane ops of minips_amd.
 
 Every op has ONE device implementation: GPU tensors go to the hand-written gfx950 HIP
-kernels in ``minips_amd._kernels`` (the evaluation, gradient-clipping and FTRL ops: in the small
-extensions ``_evalk`` / ``_optk`` / ``_ftrlk``) and raise if that extension is missing -- there is no
+kernels in ``minips_amd._kernels`` (the evaluation, gradient-clipping, FTRL and Adagrad + FTRL ops: in the small
+extensions ``_evalk`` / ``_optk`` / ``_ftrlk`` / ``_wdftrlk``) and raise if that extension is missing -- there is no
 silent eager fallback on a GPU. CPU tensors run a plain PyTorch reference of the same math;
 that path exists for the CPU/gloo plumbing configuration (BASELINE config 1) and as the fp32
 oracle the GPU numerics tests compare against.
@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import evalk, ftrlk, kernels, optk
+from .._native import evalk, ftrlk, kernels, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -566,6 +566,43 @@ def sparse_ftrl(table, zn, keys, base, grads, alpha, beta=1.0, l1=0.0, l2=0.0, n
     table[rows, :W] = ftrl_weights(z1, n1, alpha, beta, l1, l2)
     zn[rows, :W] = z1
     zn[rows, W:] = n1
+
+
+def sparse_adagrad_ftrl(table, state, zn, split, keys, base, grads, lr, eps, alpha, beta=1.0, l1=0.0, l2=0.0,
+                        grad_scale=1.0, n_dev=None, oor=None, blocks=0):
+    """Split rows with two rules, one pass: columns [0, split) of table rows keys - base take
+    sparse_rowwise_adagrad's rule (``state`` [rows], ``lr``, ``eps``), columns [split, W) take sparse_ftrl's
+    coordinate rule on ``grads[:, split:] * grad_scale`` (the scaling its own rounded product) with ``alpha``,
+    ``beta``, ``l1``, ``l2``. ``zn`` [rows, 2 * (W - split)]: z | n of the wide columns, sparse_ftrl's layout.
+    ``grad_scale``: the step pushes gradients of the mean loss; batch size x world gives the FTRL columns
+    the summed-loss gradient the paper's hyper-parameters assume (exact for a power of two). ``keys``
+    distinct; ``n_dev`` bounds the prefix without a host sync; a key whose row is outside [0, rows) is skipped
+    whole and counted into ``oor`` (int64 [1]). ``blocks`` > 0 forces the GPU grid size. The CPU path is the
+    composition of the two CPU references."""
+    lr, eps, alpha, beta, l1, l2, grad_scale = (float(v) for v in (lr, eps, alpha, beta, l1, l2, grad_scale))
+    D1 = int(split)
+    if _gpu(table):
+        wdftrlk().sparse_adagrad_ftrl(table, state, zn, D1, keys, int(base), grads, lr, eps, alpha, beta, l1, l2,
+                                      grad_scale, n_dev, oor, int(blocks))
+        return
+    W, nrows = grads.shape[1], table.shape[0]
+    if not 1 <= D1 < W:
+        raise RuntimeError(f"sparse_adagrad_ftrl: split {D1} outside [1, {W})")
+    if not (grad_scale > 0 and math.isfinite(grad_scale)):
+        raise RuntimeError(f"sparse_adagrad_ftrl: grad_scale {grad_scale} must be finite and positive")
+    if tuple(state.shape) != (nrows,):
+        raise RuntimeError(f"sparse_adagrad_ftrl: state [{nrows}] expected, got {tuple(state.shape)}")
+    n = keys.numel()
+    if n_dev is not None:
+        n = min(n, int(n_dev.reshape(-1)[0]))
+    rows, g = keys[:n] - base, grads[:n].float()
+    ok = (rows >= 0) & (rows < nrows)
+    if oor is not None:
+        oor += int((~ok).sum())
+    rows, g = rows[ok], g[ok]
+    sparse_rowwise_adagrad(table, state, rows, 0, g[:, :D1], lr, eps)
+    sparse_ftrl(table[:, D1:W], zn, rows, 0, g[:, D1:] * torch.tensor(grad_scale, dtype=torch.float32), alpha, beta,
+                l1, l2)
 
 
 def embedding_bag_fwd(rows, idx, offsets, mean=False, out=None):

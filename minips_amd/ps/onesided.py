@@ -423,7 +423,10 @@ class AsyncSparseTable(_AsyncTable, SparseTable):
                  eps: float = 1e-8, pull_dtype=torch.bfloat16, consistency: str = "ssp", staleness: int = 0,
                  split: int | None = None, table_id: int = 0, init_std: float = 0.01, seed: int = 1234,
                  route: str = "mix", columns=None, max_keys: int = 1 << 16, depth: int | None = None,
-                 asp_bound: int | None = None, value_dtype=torch.float32):
+                 asp_bound: int | None = None, value_dtype=torch.float32, wide_optimizer: str | None = None):
+        if wide_optimizer is not None:
+            raise ValueError("wide_optimizer is not available on the one-sided transport (its owner-apply kernels "
+                             "know the row-wise Adagrad only); use transport 'collective'")
         if optimizer not in ("add", "sgd", "rowwise_adagrad"):
             raise ValueError(f"sparse optimizer {optimizer!r}: add | sgd | rowwise_adagrad")
         if value_dtype not in (torch.float32, torch.bfloat16):

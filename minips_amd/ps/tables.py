@@ -908,16 +908,26 @@ class SparseTable:
     _local_apply = True  # this rank applies its pushes itself (the one-sided tables' owners apply)
     # hash tables need exact host counts (insert-on-miss must not see padding keys)
     _exact_counts = False
-    ftrl_zn = None  # FTRL-Proximal state [rows, 2 * width] (z | n), optimizer "ftrl" only
+    ftrl_zn = None  # FTRL-Proximal state (z | n): [rows, 2 * width] of optimizer "ftrl", [rows, 2 * (width - split)]
+    #                 of wide_optimizer "ftrl"
+    wide_optimizer = None  # "ftrl": the columns [split, width) are FTRL-Proximal coordinates
 
     def __init__(self, comm: Comm, num_rows: int, width: int, optimizer: str = "rowwise_adagrad",
                  lr: float = 0.01, eps: float = 1e-8, pull_dtype=torch.bfloat16, consistency: str = "bsp",
                  staleness: int = 0, split: int | None = None, table_id: int = 0, init_std: float = 0.01,
                  seed: int = 1234, p2p: bool | None = None, push_dtype=None, route: str = "mix",
-                 value_dtype=torch.float32, columns=None, ftrl_beta: float = 1.0, l1: float = 0.0, l2: float = 0.0):
+                 value_dtype=torch.float32, columns=None, ftrl_beta: float = 1.0, l1: float = 0.0, l2: float = 0.0,
+                 wide_optimizer: str | None = None, wide_lr: float = 0.1, ftrl_grad_scale: float = 1.0):
         """``optimizer`` "ftrl": per-coordinate FTRL-Proximal (ops.sparse_ftrl states the rule) with ``lr`` as
         its alpha, ``ftrl_beta``, ``l1`` and ``l2``; fp32 rows without ``split`` only. Its state is
         ``ftrl_zn`` [rows, 2 * width] (z | n per row); ``nnz()`` counts the non-zero weights.
+
+        ``wide_optimizer`` "ftrl" (with ``optimizer`` "rowwise_adagrad" and ``split``): columns [0, split)
+        keep the row-wise Adagrad, columns [split, width) become FTRL-Proximal coordinates with ``wide_lr`` as
+        their alpha, ``ftrl_beta``, ``l1``, ``l2``, on the pushed gradient times ``ftrl_grad_scale``
+        (ops.sparse_adagrad_ftrl states the rule). ``state2`` is not allocated; ``ftrl_zn`` is
+        [rows, 2 * (width - split)]; ``wide_nnz()`` counts the non-zero wide weights. Several ranks apply
+        through the generic owner path.
 
         ``value_dtype`` float64: the reference's double tables (CreateTable<double>,
         lr_example.cpp:182; values read as double, kv_client_table.hpp:96-101) -- optimizer "add"
@@ -940,6 +950,20 @@ class SparseTable:
             if not lr > 0 or ftrl_beta < 0 or l1 < 0 or l2 < 0:
                 raise ValueError(f"optimizer 'ftrl': lr (alpha) {lr} must be positive, ftrl_beta {ftrl_beta}, "
                                  f"l1 {l1} and l2 {l2} non-negative")
+        if wide_optimizer is not None:
+            if wide_optimizer != "ftrl":
+                raise ValueError(f"wide_optimizer {wide_optimizer!r}: None | 'ftrl'")
+            if optimizer != "rowwise_adagrad":
+                raise ValueError(f"wide_optimizer 'ftrl' goes beside optimizer 'rowwise_adagrad', not {optimizer!r}")
+            if split is None or not 1 <= int(split) < width:
+                raise ValueError(f"wide_optimizer 'ftrl' needs split rows: 1 <= split < width {width}, got {split}")
+            if value_dtype != torch.float32:
+                raise ValueError(f"wide_optimizer 'ftrl' keeps fp32 rows, not {value_dtype}")
+            ok = wide_lr > 0 and ftrl_beta >= 0 and l1 >= 0 and l2 >= 0 and 0 < ftrl_grad_scale < float("inf")
+            if not ok:  # (a NaN fails every comparison)
+                raise ValueError(f"wide_optimizer 'ftrl': wide_lr (alpha) {wide_lr} must be positive, ftrl_beta "
+                                 f"{ftrl_beta}, l1 {l1} and l2 {l2} non-negative, ftrl_grad_scale {ftrl_grad_scale} "
+                                 f"finite and positive")
         if value_dtype == torch.float64:
             if optimizer != "add":
                 raise ValueError("fp64 sparse tables support the reference's plain add apply only")
@@ -990,10 +1014,15 @@ class SparseTable:
             self.shard.zero_()
         self.state = torch.zeros(self._rows_alloc, dtype=torch.float32, device=dev) \
             if optimizer == "rowwise_adagrad" else None
-        self.state2 = torch.zeros_like(self.state) if (self.state is not None and split is not None) else None
+        self.wide_optimizer = wide_optimizer
+        self.wide_lr, self.ftrl_grad_scale = float(wide_lr), float(ftrl_grad_scale)
+        self.state2 = torch.zeros_like(self.state) \
+            if (self.state is not None and split is not None and wide_optimizer is None) else None
         self.ftrl_beta, self.l1, self.l2 = float(ftrl_beta), float(l1), float(l2)
         if optimizer == "ftrl":
             self.ftrl_zn = torch.zeros(self._rows_alloc, 2 * width, dtype=torch.float32, device=dev)
+        elif wide_optimizer == "ftrl":
+            self.ftrl_zn = torch.zeros(self._rows_alloc, 2 * (width - split), dtype=torch.float32, device=dev)
         self._init_comm(consistency, staleness, p2p)
 
     def _init_comm(self, consistency, staleness, p2p):
@@ -1240,9 +1269,9 @@ class SparseTable:
         with ops.owner_rows_adagrad (segment sums + apply fused, deterministic) instead of
         scatter-add into a zeroed buffer + a separate apply."""
         return (self.comm.world > 1 and self.comm.world <= 16 and self._local_apply
-                and self.optimizer == "rowwise_adagrad" and self.value_dtype == torch.float32
-                and type(self)._owner_rows is SparseTable._owner_rows and 16 < self.width <= 64
-                and self.width % 4 == 0)
+                and self.optimizer == "rowwise_adagrad" and self.wide_optimizer is None
+                and self.value_dtype == torch.float32 and type(self)._owner_rows is SparseTable._owner_rows
+                and 16 < self.width <= 64 and self.width % 4 == 0)
 
     def plan(self, keys: torch.Tensor, csr: bool = False) -> SparsePlan:
         return self._finish_plan(self._start_plan(keys, csr))
@@ -1435,7 +1464,12 @@ class SparseTable:
             ops.sparse_apply_bf16(opt, self.shard, self.state, keys, base, g.contiguous(), self.lr, self.eps, scale,
                                   state2=self.state2, split=self.split, step=self._applies, seed=self.seed, n_dev=n_dev)
             return
-        if self.optimizer == "rowwise_adagrad":
+        if self.wide_optimizer == "ftrl":
+            # (as below) a row outside the shard is skipped and counted, the count read at drain
+            ops.sparse_adagrad_ftrl(self.shard, self.state, self.ftrl_zn, self.split, keys, base, g.contiguous(),
+                                    self.lr, self.eps, self.wide_lr, self.ftrl_beta, self.l1, self.l2,
+                                    grad_scale=self.ftrl_grad_scale, n_dev=n_dev, oor=self._oor_counter())
+        elif self.optimizer == "rowwise_adagrad":
             ops.sparse_rowwise_adagrad(self.shard, self.state, keys, base, g, self.lr, self.eps,
                                        state2=self.state2, split=self.split, n_dev=n_dev)
         elif self.optimizer == "sgd":
@@ -1458,6 +1492,17 @@ class SparseTable:
         table and reads the count on the host: for report time, not the step."""
         self.drain()
         c = torch.count_nonzero(self.shard[: self.rows_local]).to(torch.int64).reshape(1)
+        if self.comm.world > 1:
+            self.comm.all_reduce_(c)
+        return int(c.item())
+
+    def wide_nnz(self) -> int:
+        """Non-zero weights in the wide columns [split, width) of the whole table (nnz()'s protocol: a
+        drain, a host read, one all-reduce)."""
+        if self.split is None:
+            raise ValueError("wide_nnz: the table has no split rows")
+        self.drain()
+        c = torch.count_nonzero(self.shard[: self.rows_local, self.split:]).to(torch.int64).reshape(1)
         if self.comm.world > 1:
             self.comm.all_reduce_(c)
         return int(c.item())
@@ -1541,7 +1586,9 @@ class HashSparseTable(SparseTable):
     def __init__(self, comm: Comm, width: int, capacity: int = 1 << 16, optimizer: str = "add", lr: float = 0.01,
                  eps: float = 1e-8, pull_dtype=torch.float32, consistency: str = "bsp", staleness: int = 0,
                  table_id: int = 0, init_std: float = 0.0, seed: int = 1234, p2p: bool | None = None,
-                 push_dtype=None):
+                 push_dtype=None, wide_optimizer: str | None = None):
+        if wide_optimizer is not None:
+            raise ValueError("wide_optimizer is not available on hash tables (SparseTable with split rows only)")
         self.comm = comm
         self.table_id = table_id
         self.push_dtype = push_dtype or torch.float32  # MapStorage values are exact sums: keep fp32

@@ -117,6 +117,12 @@ def parse(argv=None):
     ap.add_argument("--ftrl_beta", type=float, default=1.0)
     ap.add_argument("--ftrl_l1", type=float, default=0.0, help="L1 strength: weights with |z| <= l1 are exactly 0")
     ap.add_argument("--ftrl_l2", type=float, default=0.0)
+    ap.add_argument("--wide_optimizer", default="adagrad", choices=["adagrad", "ftrl"],
+                    help="W&D wide column: adagrad (its own row-wise accumulator) or ftrl (FTRL-Proximal with the "
+                         "--ftrl_* flags beside the row-wise Adagrad embedding; collective transport)")
+    ap.add_argument("--ftrl_grad_scale", type=float, default=0.0,
+                    help="--wide_optimizer ftrl: factor on the pushed mean-loss gradient of the wide columns; 0 "
+                         "(default): batch size x world, the summed-loss gradient")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -127,6 +133,13 @@ def parse(argv=None):
             ap.error(f"--sparse_optimizer ftrl keeps float32 weights, not --value_dtype {args.value_dtype}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
+    if args.wide_optimizer == "ftrl":
+        if args.model != "widedeep":
+            ap.error(f"--wide_optimizer ftrl supports --model widedeep, not {args.model}")
+        if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
+            ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
+        if not 0 <= args.ftrl_grad_scale < float("inf"):
+            ap.error("--wide_optimizer ftrl: --ftrl_grad_scale must be finite and >= 0 (0: batch size x world)")
     args.opt_flags = bool(args.clip_norm or args.lr_warmup or args.lr_decay_steps or args.lr_min_ratio)
     if args.opt_flags and args.model not in ("gpt2", "mlp"):
         ap.error(f"--clip_norm / --lr_warmup / --lr_decay_steps / --lr_min_ratio support --model gpt2 and mlp, "
@@ -143,6 +156,9 @@ def parse(argv=None):
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
         args.transport = ("onesided" if args.model in ("dlrm", "widedeep") and args.consistency in ("ssp", "asp")
                           else "collective")
+    if args.wide_optimizer == "ftrl" and args.transport == "onesided":
+        ap.error("--wide_optimizer ftrl with SSP / ASP needs --transport collective (the one-sided owners apply the "
+                 "row-wise Adagrad only)")
     if args.eval_every > 0 and args.transport == "onesided":
         ap.error("--eval_every: held-out evaluation needs --transport collective (evaluate() is not implemented "
                  "on the onesided transport)")
@@ -206,8 +222,13 @@ def build(args, comm):
         from .models.widedeep import WideDeep, WideDeepConfig
 
         B = args.batch or (64 if args.small else 16384)
+        wide = {}
+        if args.wide_optimizer == "ftrl":
+            wide = dict(wide_optimizer="ftrl", wide_alpha=args.ftrl_alpha, wide_beta=args.ftrl_beta,
+                        wide_l1=args.ftrl_l1, wide_l2=args.ftrl_l2,
+                        wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
         cfg = WideDeepConfig(consistency=args.consistency, staleness=args.staleness, transport=args.transport,
-                             max_batch=B, **({"cards": SMALL_CARDS} if args.small else {}))
+                             max_batch=B, **({"cards": SMALL_CARDS} if args.small else {}), **wide)
         m = WideDeep(cfg, comm)
         return m, {0: m.emb, 1: m.dense}, (lambda: CriteoSynth(B, cards=cfg.cards, device=dev, seed=seed)), \
             (lambda b: m.train_step(*b)), B
@@ -729,6 +750,8 @@ def main(argv=None):
     ftrl_final = {}
     if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
         ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
+    if args.wide_optimizer == "ftrl":  # likewise a collective
+        ftrl_final = dict(wide_nnz=model.wide_nnz(), wide_optimizer="ftrl")
     clip_final = {}
     if args.clip_norm:
         cs = tables[0].clip_stats()

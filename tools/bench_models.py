@@ -8,7 +8,8 @@ barrier + synchronize, max over ranks, whole-job value, one JSON line on rank 0)
 
 models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, samples/s),
         dlrm-10b (config 5 at its per-GPU shard: 1.25B rows x 64 bf16 per GPU, ASP), lr (config 1 on GPUs,
-        samples/s), kmeans (samples/s), widedeep-ssp (config 3).
+        samples/s), kmeans (samples/s), widedeep-ssp (config 3), widedeep (the same driver under BSP; takes
+        --wide_optimizer ftrl and reports wide_nnz).
 """
 from __future__ import annotations
 
@@ -117,14 +118,34 @@ def build(args, comm):
         g.manual_seed(r)
         return m, (lambda: m.train_step(torch.randn(B, cfg.dims, generator=g, device=dev))), B, "samples/s", \
             dict(model="mini-batch K-Means K=1000 D=128", seq_len=None)
-    if args.model == "widedeep-ssp":
+    if args.model in ("widedeep", "widedeep-ssp"):
         from minips_amd.data.synthetic import CriteoSynth
         from minips_amd.models.widedeep import WideDeep, WideDeepConfig
 
         B = args.batch or 16384
-        cfg = WideDeepConfig(consistency="ssp", staleness=max(1, args.staleness), transport=args.transport,
-                             max_batch=B)
+        bsp = args.model == "widedeep"
+        wide = {}
+        if args.wide_optimizer == "ftrl":
+            wide = dict(wide_optimizer="ftrl", wide_alpha=args.ftrl_alpha, wide_beta=args.ftrl_beta,
+                        wide_l1=args.ftrl_l1, wide_l2=args.ftrl_l2,
+                        wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
+        cfg = WideDeepConfig(consistency="bsp" if bsp else "ssp", staleness=0 if bsp else max(1, args.staleness),
+                             transport=args.transport, max_batch=B, **wide)
         m = WideDeep(cfg, comm)
+        if bsp:  # BSP, the look-ahead feeder below
+            from minips_amd.models.feeder import LookaheadFeeder
+            from minips_amd.models.layers import compute_priority
+
+            data = CriteoSynth(B, cards=cfg.cards, device=dev, seed=1000 + r)
+            if dev.type == "cuda":
+                main = torch.cuda.Stream(device=dev, priority=compute_priority())
+                main.wait_stream(torch.cuda.default_stream(dev))
+                torch.cuda.set_stream(main)
+            feeder = LookaheadFeeder(m, data, comm)
+            extra = dict(wide_optimizer="ftrl", ftrl=wide) if wide else {}
+            return m, feeder.step, B, "samples/s", dict(model="Wide&Deep Criteo BSP (collective)", seq_len=None,
+                                                 consistency="bsp", transport=args.transport, feeder="lookahead",
+                                                 **extra)
         data = CriteoSynth(B, cards=cfg.cards, device=dev, seed=1000 + r)
         if args.feeder == "inline":  # the next batch generated on the compute stream at step start
             state = {"cur": data.next()}
@@ -156,7 +177,7 @@ def build(args, comm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
-                                                         "widedeep-ssp"])
+                                                         "widedeep-ssp", "widedeep"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -185,7 +206,14 @@ def main():
     ap.add_argument("--ftrl_beta", type=float, default=1.0)
     ap.add_argument("--ftrl_l1", type=float, default=0.0)
     ap.add_argument("--ftrl_l2", type=float, default=0.0)
+    ap.add_argument("--wide_optimizer", "--wide-optimizer", dest="wide_optimizer", default="adagrad",
+                    choices=["adagrad", "ftrl"],
+                    help="widedeep: the wide column's rule (ftrl: FTRL-Proximal with the --ftrl_* flags; the result "
+                         "gains wide_nnz)")
+    ap.add_argument("--ftrl_grad_scale", type=float, default=0.0, help="widedeep ftrl: 0 = batch size x world")
     args = ap.parse_args()
+    if args.wide_optimizer == "ftrl" and args.model != "widedeep":
+        ap.error("--wide_optimizer ftrl: --model widedeep only")
     if args.sparse_optimizer == "ftrl" and (args.model != "lr" or args.value_dtype != "float32"):
         ap.error("--sparse_optimizer ftrl: --model lr with --value-dtype float32 only")
     if args.clip_norm and args.model != "gpt2":
@@ -216,13 +244,15 @@ def main():
     el = float(t)
     if args.sparse_optimizer == "ftrl":  # after the timed window: a host read (collective)
         cfg["nnz"] = model.nnz()
+    if args.wide_optimizer == "ftrl":  # likewise
+        cfg["wide_nnz"] = model.wide_nnz()
     if comm.rank == 0:
         print(json.dumps({
             "metric": f"{unit.split('/')[0]}/sec (whole job) {args.model} {cfg.pop('consistency', args.consistency)}",
             "value": round(per_step * comm.world * args.steps / el, 1), "unit": unit, "n_gpus": comm.world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * el / args.steps, 3),
             "higher_is_better": True, "scaling": "weak",
-            "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp")
+            "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp", "widedeep")
                       else ("fp64" if args.value_dtype == "float64" and args.model == "lr" else "fp32")),
             "data": "synthetic", "last": float(out.float().sum()) if torch.is_tensor(out) else None,
             "config": dict(cfg, parallelism=f"ps-dp{comm.world}"),

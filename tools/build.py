@@ -15,6 +15,8 @@ Targets
             small torch extension, over k_gradclip.o only)
   ftrl_py   csrc/bindings/ftrl_py.cpp    -> minips_amd/_ftrlk*.so     (the FTRL-Proximal sparse apply: a fourth
             small torch extension, over k_ftrl.o only)
+  wideftrl_py csrc/bindings/wideftrl_py.cpp -> minips_amd/_wdftrlk*.so (row-wise Adagrad + FTRL-Proximal on split
+            rows: a fifth small torch extension, over k_wideftrl.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -233,6 +235,11 @@ def build_ftrl_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "ftrl_py", "_ftrlk", "k_ftrl.o")
 
 
+def build_wideftrl_py(kobjs: list[str]) -> str:
+    """minips_amd/_wdftrlk: the Adagrad + FTRL split-row binding over k_wideftrl.o alone."""
+    return _build_small_ext(kobjs, "wideftrl_py", "_wdftrlk", "k_wideftrl.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -260,7 +267,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 def main(argv: list[str]) -> int:
     targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
-                                  "ftrl_py"}
+                                  "ftrl_py", "wideftrl_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -276,7 +283,7 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py"}:
+    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -287,6 +294,8 @@ def main(argv: list[str]) -> int:
             print("built", build_optim_py(kobjs))
         if targets & {"kernels", "ftrl_py"}:
             print("built", build_ftrl_py(kobjs))
+        if targets & {"kernels", "wideftrl_py"}:
+            print("built", build_wideftrl_py(kobjs))
     return 0
 
 
