@@ -14,6 +14,8 @@
 * ``_wdftrlk``  -- the split-row apply with two rules, row-wise Adagrad on the deep columns and FTRL-Proximal
   on the wide ones (``SparseTable(split=..., wide_optimizer="ftrl")``): a fifth small torch extension, same
   rule.
+* ``_fmk``      -- the factorization-machine forward and backward over a CSR batch of pulled rows
+  (``ops.fm_forward`` / ``ops.fm_backward``): a sixth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -74,6 +76,11 @@ def wdftrlk():
     return _load("_wdftrlk", "gfx950 HIP Adagrad + FTRL-Proximal split-row kernel")
 
 
+def fmk():
+    """Return the HIP factorization-machine kernel module or raise a loud error."""
+    return _load("_fmk", "gfx950 HIP factorization-machine kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -97,6 +104,10 @@ def ftrlk_available() -> bool:
 
 def wdftrlk_available() -> bool:
     return _available(wdftrlk)
+
+
+def fmk_available() -> bool:
+    return _available(fmk)
 
 
 def native_dir() -> str:

@@ -196,3 +196,45 @@ class SparseLRSynth:
         y = ((teacher * vals).sum(1) > 0).float()
         rowptr = torch.arange(0, (B + 1) * k, k, device=self.device, dtype=torch.int64)
         return rowptr, cols.reshape(-1), vals.reshape(-1), y
+
+
+class FMSynth:
+    """Field-structured CSR batches with a factorization-machine teacher: ``fields`` fields of ``card`` ids
+    each, one active feature per field with value 1 (feature id = field * card + id), a fixed random teacher
+    FM of rank ``k_teacher`` (factors ~ N(0, 1), linear weights ~ N(0, 0.3^2)), labels ~ Bernoulli(sigmoid(z*)).
+    next() returns (rowptr, cols, vals, labels) like SparseLRSynth."""
+
+    def __init__(self, batch: int, fields: int = 8, card: int = 32, k_teacher: int = 4, device="cpu", seed: int = 0):
+        self.batch, self.fields, self.card, self.k_teacher = batch, fields, card, k_teacher
+        self.num_dims = fields * card
+        self.device = torch.device(device)
+        g = torch.Generator(device="cpu")  # the teacher is the same on every device
+        g.manual_seed(seed)
+        self.v = torch.randn(self.num_dims, k_teacher, generator=g).to(self.device)
+        self.w = (0.3 * torch.randn(self.num_dims, generator=g)).to(self.device)
+        self.gen = torch.Generator(device=self.device)
+        self.gen.manual_seed(seed + 1)
+        self.field_base = torch.arange(fields, dtype=torch.int64, device=self.device) * card
+
+    def holdout(self, seed: int) -> "FMSynth":
+        """A held-out stream of the SAME teacher: an independent sample stream drawn from ``seed``."""
+        g = FMSynth.__new__(FMSynth)
+        g.__dict__.update(self.__dict__)
+        g.gen = torch.Generator(device=self.device)
+        g.gen.manual_seed(seed)
+        return g
+
+    def teacher_logits(self, cols2d: torch.Tensor) -> torch.Tensor:
+        v = self.v[cols2d]  # [B, F, k]
+        s = v.sum(1)
+        return self.w[cols2d].sum(1) + 0.5 * ((s * s).sum(1) - (v * v).sum((1, 2)))
+
+    def next(self):
+        B, F = self.batch, self.fields
+        ids = torch.randint(0, self.card, (B, F), generator=self.gen, device=self.device)
+        cols = ids + self.field_base
+        p = torch.sigmoid(self.teacher_logits(cols))
+        y = (torch.rand(B, generator=self.gen, device=self.device) < p).float()
+        rowptr = torch.arange(0, (B + 1) * F, F, device=self.device, dtype=torch.int64)
+        vals = torch.ones(B * F, dtype=torch.float32, device=self.device)
+        return rowptr, cols.reshape(-1), vals, y

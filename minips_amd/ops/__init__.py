@@ -1,11 +1,11 @@
 """Data-plane ops of minips_amd.
 
 Every op has ONE device implementation: GPU tensors go to the hand-written gfx950 HIP
-kernels in ``minips_amd._kernels`` (the evaluation, gradient-clipping, FTRL and Adagrad + FTRL ops: in the small
-extensions ``_evalk`` / ``_optk`` / ``_ftrlk`` / ``_wdftrlk``) and raise if that extension is missing -- there is no
-silent eager fallback on a GPU. CPU tensors run a plain PyTorch reference of the same math;
-that path exists for the CPU/gloo plumbing configuration (BASELINE config 1) and as the fp32
-oracle the GPU numerics tests compare against.
+kernels in ``minips_amd._kernels`` (the evaluation, gradient-clipping, FTRL, Adagrad + FTRL and factorization-machine
+ops: in the small extensions ``_evalk`` / ``_optk`` / ``_ftrlk`` / ``_wdftrlk`` / ``_fmk``) and raise if that
+extension is missing -- there is no silent eager fallback on a GPU. CPU tensors run a plain PyTorch reference of
+the same math; that path exists for the CPU/gloo plumbing configuration (BASELINE config 1) and as the fp32 oracle
+the GPU numerics tests compare against.
 """
 from __future__ import annotations
 
@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import evalk, ftrlk, kernels, optk, wdftrlk
+from .._native import evalk, fmk, ftrlk, kernels, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -792,6 +792,78 @@ def wd_emb_backward(dX, dwide, inv, F, D, grad_rows, x_off=0, csr=None, sorted_r
         acc[:, D].index_add_(0, inv, dwide.repeat_interleave(F))
     if acc is not grad_rows:
         grad_rows.copy_(acc)
+    return grad_rows
+
+
+# ----------------------------------------------------------------------------- factorization machine
+def _fm_check_k(k: int, width: int):
+    if k % 4 or not 4 <= k <= 60:
+        raise RuntimeError(f"fm: k is {k}, expected k % 4 == 0 and 4 <= k <= 60")
+    if width < k + 4:
+        raise RuntimeError(f"fm: rows are {width} wide, expected >= k + 4 = {k + 4}")
+
+
+def fm_forward(rowptr, inv, vals, labels, rows, k, w0=None, gscale=1.0, blocks=0):
+    """2-way factorization machine over a CSR batch of pulled rows [v_0 .. v_{k-1} | w | pad] (the rule:
+    csrc/kernels/fm.h). Sample b holds the lookups j in [rowptr[b], rowptr[b+1]); lookup j reads rows[inv[j]]
+    with value vals[j]. y = labels > 0.5. Returns fp32 (S [B, k], z [B], dz [B], loss [B]) and rowid int32 [n]:
+      S_bf = sum_j v_f x,  z = w0 + sum_j w x + (sum_f S_bf^2 - sum_j sum_f (v_f x)^2) / 2,
+      loss = max(z, 0) - z y + log1p(exp(-|z|)),  dz = (sigmoid(z) - y) * gscale,  rowid[j] = b.
+    ``w0``: fp32 tensor whose first element is the bias (None: 0). ``blocks`` > 0 forces the GPU grid size.
+    One fused gfx950 launch on the GPU (no atomics, the same bits for every grid size); the CPU path is
+    the fp32 PyTorch reference of the same rule."""
+    k, B, n = int(k), rowptr.numel() - 1, inv.numel()
+    if _gpu(rows):
+        dev = rows.device
+        S = torch.empty(B, k, dtype=torch.float32, device=dev)
+        z, dz, loss = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+        rowid = torch.empty(n, dtype=torch.int32, device=dev)
+        fmk().fm_forward(rowptr, inv, vals, labels, rows, k, w0, float(gscale), S, z, dz, loss, rowid, int(blocks))
+        return S, z, dz, loss, rowid
+    _fm_check_k(k, rows.shape[1])
+    rowid = torch.repeat_interleave(torch.arange(B, dtype=torch.int64), rowptr[1:] - rowptr[:-1])
+    x = vals.float()
+    p = rows[inv, :k].float() * x[:, None]
+    S = torch.zeros(B, k, dtype=torch.float32).index_add_(0, rowid, p)
+    Q = torch.zeros(B, dtype=torch.float32).index_add_(0, rowid, (p * p).sum(1))
+    lin = torch.zeros(B, dtype=torch.float32).index_add_(0, rowid, rows[inv, k].float() * x)
+    z = lin + 0.5 * ((S * S).sum(1) - Q)
+    if w0 is not None:
+        z = z + w0.reshape(-1)[0].float()
+    y = (labels > 0.5).float()
+    loss = z.clamp(min=0) - z * y + torch.log1p(torch.exp(-z.abs()))
+    dz = (torch.sigmoid(z) - y) * torch.tensor(float(gscale), dtype=torch.float32)
+    return S, z, dz, loss, rowid.to(torch.int32)
+
+
+def fm_backward(inv, rowid, vals, dz, S, rows, k, grad_rows, csr=None, blocks=0):
+    """Gradient of every unique pulled row of fm_forward's batch (csrc/kernels/fm.h): with c_m = dz[rowid[m]] *
+    vals[m] over the lookups m of row u (inv[m] == u), grad_rows[u, f] = sum_m c_m (S[rowid[m], f] - rows[u, f]
+    vals[m]) for f < k, grad_rows[u, k] = sum_m c_m, columns k+1.. are 0; rows without lookups are left
+    untouched. ``csr`` = (members, memrow): the lookups grouped by unique row (a plan's lookup CSR; built from
+    ``inv`` here when absent on the GPU, ignored on the CPU). On the GPU every such row is written exactly once
+    in a fixed summation order -- no atomics, the same bits on every run and for every grid size (``blocks``);
+    the CPU reference sums with index_add_ over ``inv``."""
+    k = int(k)
+    if _gpu(rows):
+        if csr is None:
+            csr = emb_build_csr(inv, 1, max(rows.shape[0], 1))
+        fmk().fm_backward(csr[0], csr[1], rowid, vals, dz, S, rows, k, grad_rows, int(blocks))
+        return grad_rows
+    _fm_check_k(k, rows.shape[1])
+    W = k + 4
+    if grad_rows.shape[1] != W or grad_rows.shape[0] < rows.shape[0]:
+        raise RuntimeError(f"fm_backward: grad_rows {tuple(grad_rows.shape)}, expected [>= {rows.shape[0]}, {W}]")
+    if inv.numel() == 0:
+        return grad_rows
+    b, x = rowid.long(), vals.float()
+    c = dz[b] * x
+    acc = torch.zeros(rows.shape[0], W, dtype=torch.float32)
+    acc[:, :k].index_add_(0, inv, c[:, None] * (S[b] - rows[inv, :k].float() * x[:, None]))
+    acc[:, k].index_add_(0, inv, c)
+    touched = torch.zeros(rows.shape[0], dtype=torch.bool)
+    touched[inv] = True
+    grad_rows[: rows.shape[0]][touched] = acc[touched]
     return grad_rows
 
 

@@ -32,7 +32,7 @@ def _flag_bool(v):
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans"])
+    ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -123,6 +123,11 @@ def parse(argv=None):
     ap.add_argument("--ftrl_grad_scale", type=float, default=0.0,
                     help="--wide_optimizer ftrl: factor on the pushed mean-loss gradient of the wide columns; 0 "
                          "(default): batch size x world, the summed-loss gradient")
+    ap.add_argument("--fm_k", type=int, default=16, help="fm: factors per feature (k % 4 == 0, 4 <= k <= 60)")
+    ap.add_argument("--fm_fields", type=int, default=0,
+                    help="fm, synthetic data: fields per sample, one active feature each (0: 8 with --small, else 64)")
+    ap.add_argument("--fm_card", type=int, default=0,
+                    help="fm, synthetic data: ids per field (0: 32 with --small, else 262144)")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -134,8 +139,8 @@ def parse(argv=None):
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     if args.wide_optimizer == "ftrl":
-        if args.model != "widedeep":
-            ap.error(f"--wide_optimizer ftrl supports --model widedeep, not {args.model}")
+        if args.model not in ("widedeep", "fm"):
+            ap.error(f"--wide_optimizer ftrl supports --model widedeep and fm, not {args.model}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
         if not 0 <= args.ftrl_grad_scale < float("inf"):
@@ -151,8 +156,19 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "dlrm"):
-        ap.error(f"--eval_every: held-out evaluation supports --model widedeep and dlrm, not {args.model}")
+    if args.eval_every > 0 and args.model not in ("widedeep", "dlrm", "fm"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, dlrm and fm, not {args.model}")
+    if args.model == "fm":
+        if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
+            ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
+        if args.transport == "onesided":
+            ap.error("--model fm needs --transport collective (no fm on the one-sided transport)")
+        if args.kStorageType != "vector":
+            ap.error("--model fm needs --kStorageType Vector (no fm on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model fm keeps float32 rows, not --value_dtype {args.value_dtype}")
+        if args.eval_every > 0 and args.input:
+            ap.error("--model fm: --eval_every needs the synthetic stream (an --input file has no held-out split)")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
         args.transport = ("onesided" if args.model in ("dlrm", "widedeep") and args.consistency in ("ssp", "asp")
                           else "collective")
@@ -171,6 +187,18 @@ def _ftrl_kw(args) -> dict:
         return {}
     return dict(optimizer="ftrl", ftrl_alpha=args.ftrl_alpha, ftrl_beta=args.ftrl_beta, l1=args.ftrl_l1,
                 l2=args.ftrl_l2)
+
+
+def _fm_cfg(args, comm, nd: int, B: int):
+    """FMConfig of --model fm (--wide_optimizer ftrl: the linear column on FTRL with the --ftrl_* flags)."""
+    from .models.fm import FMConfig
+
+    lin = {}
+    if args.wide_optimizer == "ftrl":
+        lin = dict(linear_optimizer="ftrl", linear_alpha=args.ftrl_alpha, linear_beta=args.ftrl_beta,
+                   linear_l1=args.ftrl_l1, linear_l2=args.ftrl_l2, linear_grad_scale=args.ftrl_grad_scale)
+    return FMConfig(num_dims=nd, k=args.fm_k, lr=args.alpha, consistency=args.consistency, staleness=args.staleness,
+                    seed=args.seed, **lin)
 
 
 def _load_input(args, comm):
@@ -294,6 +322,32 @@ def build(args, comm):
             (lambda: _Skippable(_WorkerGroup([SparseLRSynth(B, num_dims=nd, nnz=16 if args.small else 64, device=dev,
                                                             seed=seed + _WSEED * w) for w in range(W)]))), \
             (lambda b: -m.train_step(*b)), B * W
+    if args.model == "fm" and args.input:
+        # a libsvm file through the LR loader path: the shard resident in HBM, batches cut on the device
+        from .models.fm import FM
+
+        shard = args._shard.to(dev)
+        nd = args.num_dims
+        if not nd:  # every rank must size the table alike: max feature id over all shards
+            t = torch.tensor([float(shard.cols.max()) + 1 if shard.cols.numel() else 1.0], device=dev)
+            comm.all_reduce_(t, op=dist.ReduceOp.MAX)
+            nd = int(t.item())
+        B = args.batch or 1024
+        m = FM(_fm_cfg(args, comm, nd, B), comm)
+        return m, {0: m.table, **({1: m.bias} if m.bias is not None else {})}, \
+            (lambda: _Skippable(_Batches(shard, B, seed))), (lambda b: m.train_step(*b)), B
+    if args.model == "fm":
+        from .data.synthetic import FMSynth
+        from .models.fm import FM
+
+        fields = args.fm_fields or (8 if args.small else 64)
+        card = args.fm_card or (32 if args.small else 262144)
+        B = args.batch or (128 if args.small else 65536)
+        m = FM(_fm_cfg(args, comm, fields * card, B), comm)
+        # one teacher for every rank (seed), this rank's own sample stream
+        return m, {0: m.table, **({1: m.bias} if m.bias is not None else {})}, \
+            (lambda: _Skippable(FMSynth(B, fields=fields, card=card, device=dev, seed=args.seed).holdout(seed + 1))), \
+            (lambda b: m.train_step(*b)), B
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
         # shard stays resident in HBM and batches are consecutive rows, cut on the device
@@ -515,7 +569,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans") and args.input:
+    if args.model in ("lr", "kmeans", "fm") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -750,7 +804,9 @@ def main(argv=None):
     ftrl_final = {}
     if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
         ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
-    if args.wide_optimizer == "ftrl":  # likewise a collective
+    if args.wide_optimizer == "ftrl" and args.model == "fm":  # likewise a collective
+        ftrl_final = dict(linear_nnz=model.linear_nnz(), wide_optimizer="ftrl")
+    elif args.wide_optimizer == "ftrl":  # likewise a collective
         ftrl_final = dict(wide_nnz=model.wide_nnz(), wide_optimizer="ftrl")
     clip_final = {}
     if args.clip_norm:

@@ -108,6 +108,22 @@ def build(args, comm):
         extra = dict(sparse_optimizer="ftrl", ftrl=ftrl) if ftrl else {}
         return m, (lambda: m.train_step(*data.next())), B, "samples/s", \
             dict(model=f"sparse LR, 16.6M features, 64 nnz/row, {args.value_dtype} table", seq_len=None, **extra)
+    if args.model == "fm":
+        from minips_amd.data.synthetic import FMSynth
+        from minips_amd.models.fm import FM, FMConfig
+
+        B = args.batch or 65536
+        fields, card = 64, 262144  # 16.8M features, 64 nnz/row: sparse LR's shape
+        lin = {}
+        if args.wide_optimizer == "ftrl":
+            lin = dict(linear_optimizer="ftrl", linear_alpha=args.ftrl_alpha, linear_beta=args.ftrl_beta,
+                       linear_l1=args.ftrl_l1, linear_l2=args.ftrl_l2, linear_grad_scale=args.ftrl_grad_scale)
+        m = FM(FMConfig(num_dims=fields * card, k=args.fm_k, consistency=args.consistency, staleness=args.staleness,
+                        **lin), comm)
+        data = FMSynth(B, fields=fields, card=card, device=dev, seed=0).holdout(1000 + r)
+        return m, (lambda: m.train_step(*data.next())), B, "samples/s", \
+            dict(model=f"factorization machine k={args.fm_k}, {fields * card} features, {fields} nnz/row, fp32 rows "
+                       f"of {args.fm_k + 4}", seq_len=None, **({"linear_optimizer": "ftrl"} if lin else {}))
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -177,7 +193,7 @@ def build(args, comm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
-                                                         "widedeep-ssp", "widedeep"])
+                                                         "widedeep-ssp", "widedeep", "fm"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -211,9 +227,10 @@ def main():
                     help="widedeep: the wide column's rule (ftrl: FTRL-Proximal with the --ftrl_* flags; the result "
                          "gains wide_nnz)")
     ap.add_argument("--ftrl_grad_scale", type=float, default=0.0, help="widedeep ftrl: 0 = batch size x world")
+    ap.add_argument("--fm_k", "--fm-k", dest="fm_k", type=int, default=16, help="fm: factors per feature")
     args = ap.parse_args()
-    if args.wide_optimizer == "ftrl" and args.model != "widedeep":
-        ap.error("--wide_optimizer ftrl: --model widedeep only")
+    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "fm"):
+        ap.error("--wide_optimizer ftrl: --model widedeep and fm only")
     if args.sparse_optimizer == "ftrl" and (args.model != "lr" or args.value_dtype != "float32"):
         ap.error("--sparse_optimizer ftrl: --model lr with --value-dtype float32 only")
     if args.clip_norm and args.model != "gpt2":
@@ -244,7 +261,9 @@ def main():
     el = float(t)
     if args.sparse_optimizer == "ftrl":  # after the timed window: a host read (collective)
         cfg["nnz"] = model.nnz()
-    if args.wide_optimizer == "ftrl":  # likewise
+    if args.wide_optimizer == "ftrl" and args.model == "fm":  # likewise
+        cfg["linear_nnz"] = model.linear_nnz()
+    elif args.wide_optimizer == "ftrl":  # likewise
         cfg["wide_nnz"] = model.wide_nnz()
     if comm.rank == 0:
         print(json.dumps({
