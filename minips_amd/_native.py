@@ -16,6 +16,8 @@
   rule.
 * ``_fmk``      -- the factorization-machine forward and backward over a CSR batch of pulled rows
   (``ops.fm_forward`` / ``ops.fm_backward``): a sixth small torch extension, same rule.
+* ``_dfmk``     -- DeepFM's FM interaction term over the assembled Wide & Deep input (``ops.wd_fm_forward`` /
+  ``ops.wd_fm_backward``): a seventh small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -81,6 +83,11 @@ def fmk():
     return _load("_fmk", "gfx950 HIP factorization-machine kernels")
 
 
+def dfmk():
+    """Return the HIP DeepFM interaction-term kernel module or raise a loud error."""
+    return _load("_dfmk", "gfx950 HIP DeepFM interaction-term kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -108,6 +115,10 @@ def wdftrlk_available() -> bool:
 
 def fmk_available() -> bool:
     return _available(fmk)
+
+
+def dfmk_available() -> bool:
+    return _available(dfmk)
 
 
 def native_dir() -> str:

@@ -71,6 +71,11 @@ class WideDeepConfig:
     wide_l1: float = 0.0
     wide_l2: float = 0.0
     wide_grad_scale: float = 1.0
+    # DeepFM (Guo et al., 2017): the factorization-machine second-order term over the F field embeddings the
+    # deep tower reads, added to the wide logit (ops.wd_fm_forward after the assembly) and to the embedding
+    # gradient (ops.wd_fm_backward after the dX dgrad). No new parameter, table state or collective; the
+    # checkpoints are Wide&Deep's. Collective transport only, emb_dim in [1, 64].
+    fm_term: bool = False
 
     def __post_init__(self):
         if self.transport == "auto":
@@ -82,6 +87,11 @@ class WideDeepConfig:
         if self.wide_optimizer == "ftrl" and self.transport == "onesided":
             raise ValueError("wide_optimizer 'ftrl' needs transport 'collective' (the one-sided owners apply the "
                              "row-wise Adagrad only)")
+        if self.fm_term and "onesided" in (self.transport, self.dense_transport):
+            raise ValueError("fm_term needs transport 'collective' (the DeepFM term is not built for the one-sided "
+                             "transport)")
+        if self.fm_term and not 1 <= self.emb_dim <= 64:
+            raise ValueError(f"fm_term: emb_dim is {self.emb_dim}, expected 1 <= emb_dim <= 64")
 
     @property
     def F(self):
@@ -280,6 +290,8 @@ class WideDeep(LookaheadPlans):
                 dwide=torch.empty(B, dtype=torch.float32, device=dev),
                 loss=torch.zeros(1, dtype=torch.float32, device=dev),
             )
+            if cfg.fm_term:  # the per-sample column sums of the embeddings, kept for the backward
+                self._bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
         return self._bufs[B]
 
     def _forward(self, b, P):
@@ -297,6 +309,8 @@ class WideDeep(LookaheadPlans):
         P = self.dense.get()
         F, D = self.cfg.F, self.cfg.emb_dim
         ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
+        if self.cfg.fm_term:
+            ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
         self._forward(b, P)
         h = self.cfg.hidden[-1]
         w4 = self.view(P, "w4").float()
@@ -313,6 +327,8 @@ class WideDeep(LookaheadPlans):
             X[:, self.k_in[0]] = 1.0
             bufs[B] = dict(X=X, wide=torch.empty(B, dtype=torch.float32, device=dev),
                            **{f"H{i + 1}": torch.empty(B, n, **bf) for i, n in enumerate(cfg.hidden)})
+            if cfg.fm_term:
+                bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
         return bufs[B]
 
     def evaluate(self, batches, evaluator=None) -> dict:
@@ -341,6 +357,8 @@ class WideDeep(LookaheadPlans):
             b = self._eval_buffers(dense.shape[0])
             rows, plan = self.emb.get(keys, plan=self.emb.plan(keys))  # (not _take_plan: look-ahead plans survive)
             ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
+            if cfg.fm_term:
+                ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
             self._forward(b, P)
             ev.update_head(b["H3"], w4[:h], w4[h:h + 1], b["wide"], labels)
         ev.reduce(self.comm)
@@ -390,6 +408,8 @@ class WideDeep(LookaheadPlans):
         else:
             rows, plan = self.emb.get(keys, plan=plan)
             ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0], zero=b["loss"])
+        if cfg.fm_term:  # DeepFM: wide += the FM term of the embeddings just assembled (before the head reads it)
+            ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
         if pend_side is not None:  # ... and its dense Adam ran (side stream) before the forward reads W
             streams.current(self.comm.device).wait_event(pend_side[1])
         ph.__exit__(None, None, None)
@@ -439,6 +459,8 @@ class WideDeep(LookaheadPlans):
             ops.linear_dgrad(b["dH1"], self.view(P, "W1"), n_cols=F * D, out=b["dX"])
         # W's last reader of the step is issued: a side-stream dense Adam may start after this point
         w_read = side.point() if _ADAM_AFTER_DGRAD and self.comm.world == 1 else None
+        if cfg.fm_term:  # DeepFM: dX += dz (S - v) per lookup, in the order the dgrad wrote the rows
+            ops.wd_fm_backward(b["X"], b["S"], b["dwide"], b["dX"], F, D, perm=plan.csr[2] if sorted_rows else None)
         if _W1_LATE:  # the layer-1 weight gradient beside the memory-bound embedding backward instead
             with side.fork():
                 _wgrad(b["dH1"], b["X"], self.view(G, "W1"), sink)

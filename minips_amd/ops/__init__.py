@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import evalk, fmk, ftrlk, kernels, optk, wdftrlk
+from .._native import dfmk, evalk, fmk, ftrlk, kernels, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -694,6 +694,62 @@ def wd_head_fold(B, Hd, dw, db, loss_sum, dH_colsum=None):
     stream (recordable into a LaunchList). No-op on the CPU (wd_head added them)."""
     if _gpu(dw):
         (kernels() if _REC is None else _REC.lst).wd_head_fold(int(B), int(Hd), dw, db, loss_sum, dH_colsum)
+
+
+# ----------------------------------------------------------------------------- DeepFM's interaction term
+def _wd_fm_check(X, F, D):
+    if not 1 <= D <= 64 or F < 1:
+        raise RuntimeError(f"wd_fm: D is {D} and F is {F}, expected 1 <= D <= 64 and F >= 1")
+    if X.dim() != 2 or X.shape[1] < F * D:
+        raise RuntimeError(f"wd_fm: X has shape {tuple(X.shape)}, expected [B, >= F * D = {F * D}]")
+
+
+def wd_fm_forward(X, F, D, wide, S=None, blocks=0):
+    """DeepFM's second-order term over the assembled Wide&Deep input (the rule: csrc/kernels/deepfm.h). X bf16
+    [B, >= F*D] holds sample b's F field embeddings in columns [f*D, f*D + D); with v = X[:, :F*D].float():
+      S_bc = sum_f v_fc,  q_bc = sum_f v_fc^2,  wide[b] += 0.5 * sum_c (S_bc^2 - q_bc)   (all fp32).
+    Returns S fp32 [B, D] (``S``: written in place when given, no allocation). Columns >= F*D of X are never
+    read. ``blocks`` > 0 forces the GPU grid size. One gfx950 launch on the GPU (one wave per sample, no atomics,
+    the same bits for every grid size); the CPU path is the fp32 PyTorch reference of the same rule."""
+    F, D, B = int(F), int(D), X.shape[0]
+    if S is None:
+        S = torch.empty(B, D, dtype=torch.float32, device=X.device)
+    if _gpu(X):
+        dfmk().wd_fm_forward(X, F, D, wide, S, int(blocks))
+        return S
+    _wd_fm_check(X, F, D)
+    v = X[:, : F * D].float().reshape(B, F, D)
+    s = v.sum(1)
+    S.copy_(s)
+    wide += 0.5 * (s * s - (v * v).sum(1)).sum(1)
+    return S
+
+
+def wd_fm_backward(X, S, dwide, dX, F, D, perm=None, blocks=0):
+    """The interaction term's gradient added to the embedding gradient (csrc/kernels/deepfm.h): for every lookup
+    (b, f), row r = perm[b*F + f] (b*F + f without ``perm``) of ``dX`` (bf16, B*F*D contiguous elements) viewed as
+    [B*F, D] becomes bf16(dX[r].float() + dwide[b] * (S[b] - v_bf)) -- three fp32 roundings and one to bf16. A
+    ``perm`` (int32) entry outside [0, B*F) is skipped. In place; the CPU path computes the same bits."""
+    F, D, B = int(F), int(D), X.shape[0]
+    if _gpu(X):
+        dfmk().wd_fm_backward(X, S, dwide, perm, dX, F, D, int(blocks))
+        return dX
+    _wd_fm_check(X, F, D)
+    n = B * F
+    if dX.numel() != n * D or not dX.is_contiguous():
+        raise RuntimeError(f"wd_fm_backward: dX {tuple(dX.shape)}, expected {n * D} contiguous elements")
+    v = X[:, : F * D].float().reshape(n, D)
+    dx = dX.view(n, D)
+    Sb = S.repeat_interleave(F, 0)
+    dz = dwide.repeat_interleave(F)[:, None]
+    if perm is None:
+        dx.copy_((dx.float() + dz * (Sb - v)).to(torch.bfloat16))
+        return dX
+    r = perm.long()
+    ok = (r >= 0) & (r < n)
+    r = r[ok]
+    dx[r] = (dx[r].float() + dz[ok] * (Sb[ok] - v[ok])).to(torch.bfloat16)
+    return dX
 
 
 # ----------------------------------------------------------------------------- held-out evaluation

@@ -8,6 +8,8 @@ checkpoint_toggle, checkpoint_file_prefix, use_weight_file, heartbeat_interval, 
 report_interval, with_injected_straggler, kModelType (= --consistency), kStaleness, batch_size,
 num_iters (= --steps), alpha (LR). Extra: --fail_rank/--fail_step fault injection, --metrics_dir,
 --eval_every/--eval_batches/--eval_seed (held-out AUC and log loss of widedeep / dlrm; off by default).
+--model deepfm is widedeep with the FM second-order term over its field embeddings (WideDeepConfig(fm_term=True)):
+every widedeep flag applies, the final JSON gains fm_term, SSP / ASP need --transport collective.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -32,7 +34,8 @@ def _flag_bool(v):
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm"])
+    ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
+                                                             "deepfm"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -139,8 +142,8 @@ def parse(argv=None):
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     if args.wide_optimizer == "ftrl":
-        if args.model not in ("widedeep", "fm"):
-            ap.error(f"--wide_optimizer ftrl supports --model widedeep and fm, not {args.model}")
+        if args.model not in ("widedeep", "deepfm", "fm"):
+            ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm and fm, not {args.model}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
         if not 0 <= args.ftrl_grad_scale < float("inf"):
@@ -156,8 +159,9 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "dlrm", "fm"):
-        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, dlrm and fm, not {args.model}")
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dlrm", "fm"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dlrm and fm, not "
+                 f"{args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -170,8 +174,11 @@ def parse(argv=None):
         if args.eval_every > 0 and args.input:
             ap.error("--model fm: --eval_every needs the synthetic stream (an --input file has no held-out split)")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
-        args.transport = ("onesided" if args.model in ("dlrm", "widedeep") and args.consistency in ("ssp", "asp")
-                          else "collective")
+        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm")
+                          and args.consistency in ("ssp", "asp") else "collective")
+    if args.model == "deepfm" and args.transport == "onesided":
+        ap.error("--model deepfm with SSP / ASP needs --transport collective (the FM term is not built for the "
+                 "one-sided transport)")
     if args.wide_optimizer == "ftrl" and args.transport == "onesided":
         ap.error("--wide_optimizer ftrl with SSP / ASP needs --transport collective (the one-sided owners apply the "
                  "row-wise Adagrad only)")
@@ -245,7 +252,7 @@ def build(args, comm):
     dev = comm.device
     r = comm.rank
     seed = args.seed * 1000 + r
-    if args.model == "widedeep":
+    if args.model in ("widedeep", "deepfm"):  # deepfm: the same model with the FM term over its embeddings
         from .data.synthetic import CriteoSynth
         from .models.widedeep import WideDeep, WideDeepConfig
 
@@ -256,7 +263,8 @@ def build(args, comm):
                         wide_l1=args.ftrl_l1, wide_l2=args.ftrl_l2,
                         wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
         cfg = WideDeepConfig(consistency=args.consistency, staleness=args.staleness, transport=args.transport,
-                             max_batch=B, **({"cards": SMALL_CARDS} if args.small else {}), **wide)
+                             max_batch=B, fm_term=args.model == "deepfm",
+                             **({"cards": SMALL_CARDS} if args.small else {}), **wide)
         m = WideDeep(cfg, comm)
         return m, {0: m.emb, 1: m.dense}, (lambda: CriteoSynth(B, cards=cfg.cards, device=dev, seed=seed)), \
             (lambda b: m.train_step(*b)), B
@@ -808,6 +816,8 @@ def main(argv=None):
         ftrl_final = dict(linear_nnz=model.linear_nnz(), wide_optimizer="ftrl")
     elif args.wide_optimizer == "ftrl":  # likewise a collective
         ftrl_final = dict(wide_nnz=model.wide_nnz(), wide_optimizer="ftrl")
+    if args.model == "deepfm":
+        ftrl_final["fm_term"] = True
     clip_final = {}
     if args.clip_norm:
         cs = tables[0].clip_stats()

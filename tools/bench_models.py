@@ -9,7 +9,8 @@ barrier + synchronize, max over ranks, whole-job value, one JSON line on rank 0)
 models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, samples/s),
         dlrm-10b (config 5 at its per-GPU shard: 1.25B rows x 64 bf16 per GPU, ASP), lr (config 1 on GPUs,
         samples/s), kmeans (samples/s), widedeep-ssp (config 3), widedeep (the same driver under BSP; takes
-        --wide_optimizer ftrl and reports wide_nnz).
+        --wide_optimizer ftrl and reports wide_nnz), deepfm (widedeep with the FM term over its embeddings,
+        WideDeepConfig(fm_term=True)).
 """
 from __future__ import annotations
 
@@ -134,19 +135,20 @@ def build(args, comm):
         g.manual_seed(r)
         return m, (lambda: m.train_step(torch.randn(B, cfg.dims, generator=g, device=dev))), B, "samples/s", \
             dict(model="mini-batch K-Means K=1000 D=128", seq_len=None)
-    if args.model in ("widedeep", "widedeep-ssp"):
+    if args.model in ("widedeep", "widedeep-ssp", "deepfm"):
         from minips_amd.data.synthetic import CriteoSynth
         from minips_amd.models.widedeep import WideDeep, WideDeepConfig
 
         B = args.batch or 16384
-        bsp = args.model == "widedeep"
+        bsp = args.model in ("widedeep", "deepfm")
+        fm_term = args.model == "deepfm"
         wide = {}
         if args.wide_optimizer == "ftrl":
             wide = dict(wide_optimizer="ftrl", wide_alpha=args.ftrl_alpha, wide_beta=args.ftrl_beta,
                         wide_l1=args.ftrl_l1, wide_l2=args.ftrl_l2,
                         wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
         cfg = WideDeepConfig(consistency="bsp" if bsp else "ssp", staleness=0 if bsp else max(1, args.staleness),
-                             transport=args.transport, max_batch=B, **wide)
+                             transport=args.transport, max_batch=B, fm_term=fm_term, **wide)
         m = WideDeep(cfg, comm)
         if bsp:  # BSP, the look-ahead feeder below
             from minips_amd.models.feeder import LookaheadFeeder
@@ -159,7 +161,10 @@ def build(args, comm):
                 torch.cuda.set_stream(main)
             feeder = LookaheadFeeder(m, data, comm)
             extra = dict(wide_optimizer="ftrl", ftrl=wide) if wide else {}
-            return m, feeder.step, B, "samples/s", dict(model="Wide&Deep Criteo BSP (collective)", seq_len=None,
+            if fm_term:
+                extra["fm_term"] = True
+            name = "DeepFM (Wide&Deep + FM term)" if fm_term else "Wide&Deep"
+            return m, feeder.step, B, "samples/s", dict(model=f"{name} Criteo BSP (collective)", seq_len=None,
                                                  consistency="bsp", transport=args.transport, feeder="lookahead",
                                                  **extra)
         data = CriteoSynth(B, cards=cfg.cards, device=dev, seed=1000 + r)
@@ -193,7 +198,7 @@ def build(args, comm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
-                                                         "widedeep-ssp", "widedeep", "fm"])
+                                                         "widedeep-ssp", "widedeep", "fm", "deepfm"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -229,8 +234,8 @@ def main():
     ap.add_argument("--ftrl_grad_scale", type=float, default=0.0, help="widedeep ftrl: 0 = batch size x world")
     ap.add_argument("--fm_k", "--fm-k", dest="fm_k", type=int, default=16, help="fm: factors per feature")
     args = ap.parse_args()
-    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "fm"):
-        ap.error("--wide_optimizer ftrl: --model widedeep and fm only")
+    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "fm"):
+        ap.error("--wide_optimizer ftrl: --model widedeep, deepfm and fm only")
     if args.sparse_optimizer == "ftrl" and (args.model != "lr" or args.value_dtype != "float32"):
         ap.error("--sparse_optimizer ftrl: --model lr with --value-dtype float32 only")
     if args.clip_norm and args.model != "gpt2":
@@ -271,7 +276,7 @@ def main():
             "value": round(per_step * comm.world * args.steps / el, 1), "unit": unit, "n_gpus": comm.world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * el / args.steps, 3),
             "higher_is_better": True, "scaling": "weak",
-            "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp", "widedeep")
+            "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp", "widedeep", "deepfm")
                       else ("fp64" if args.value_dtype == "float64" and args.model == "lr" else "fp32")),
             "data": "synthetic", "last": float(out.float().sum()) if torch.is_tensor(out) else None,
             "config": dict(cfg, parallelism=f"ps-dp{comm.world}"),

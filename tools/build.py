@@ -19,6 +19,8 @@ Targets
             rows: a fifth small torch extension, over k_wideftrl.o only)
   fm_py     csrc/bindings/fm_py.cpp      -> minips_amd/_fmk*.so      (the factorization-machine forward and
             backward: a sixth small torch extension, over k_fm.o only)
+  deepfm_py csrc/bindings/deepfm_py.cpp  -> minips_amd/_dfmk*.so     (DeepFM's FM interaction term on the Wide & Deep
+            input: a seventh small torch extension, over k_deepfm.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -247,6 +249,11 @@ def build_fm_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "fm_py", "_fmk", "k_fm.o")
 
 
+def build_deepfm_py(kobjs: list[str]) -> str:
+    """minips_amd/_dfmk: the DeepFM interaction-term binding over k_deepfm.o alone."""
+    return _build_small_ext(kobjs, "deepfm_py", "_dfmk", "k_deepfm.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -274,7 +281,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 def main(argv: list[str]) -> int:
     targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
-                                  "ftrl_py", "wideftrl_py", "fm_py"}
+                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -290,7 +297,7 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py"}:
+    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -305,6 +312,8 @@ def main(argv: list[str]) -> int:
             print("built", build_wideftrl_py(kobjs))
         if targets & {"kernels", "fm_py"}:
             print("built", build_fm_py(kobjs))
+        if targets & {"kernels", "deepfm_py"}:
+            print("built", build_deepfm_py(kobjs))
     return 0
 
 
