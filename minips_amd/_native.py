@@ -18,6 +18,8 @@
   (``ops.fm_forward`` / ``ops.fm_backward``): a sixth small torch extension, same rule.
 * ``_dfmk``     -- DeepFM's FM interaction term over the assembled Wide & Deep input (``ops.wd_fm_forward`` /
   ``ops.wd_fm_backward``): a seventh small torch extension, same rule.
+* ``_dcnk``     -- the Deep & Cross layers over the assembled Wide & Deep input (``ops.wd_cross_forward`` /
+  ``ops.wd_cross_backward`` / ``ops.wd_cross_fold``): an eighth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -88,6 +90,11 @@ def dfmk():
     return _load("_dfmk", "gfx950 HIP DeepFM interaction-term kernels")
 
 
+def dcnk():
+    """Return the HIP Deep & Cross kernel module or raise a loud error."""
+    return _load("_dcnk", "gfx950 HIP Deep & Cross kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -119,6 +126,10 @@ def fmk_available() -> bool:
 
 def dfmk_available() -> bool:
     return _available(dfmk)
+
+
+def dcnk_available() -> bool:
+    return _available(dcnk)
 
 
 def native_dir() -> str:

@@ -76,6 +76,13 @@ class WideDeepConfig:
     # gradient (ops.wd_fm_backward after the dX dgrad). No new parameter, table state or collective; the
     # checkpoints are Wide&Deep's. Collective transport only, emb_dim in [1, 64].
     fm_term: bool = False
+    # Deep & Cross (Wang et al., 2017): cross_layers = L > 0 vector-weight cross layers x_{l+1} = x_0 <x_l, w_l> + b_l
+    # + x_l over the whole assembled input (embeddings and dense features, d = F * emb_dim + n_dense columns), whose
+    # output enters the wide logit through one more vector w_c (ops.wd_cross_forward after the assembly and after the
+    # DeepFM term; ops.wd_cross_backward / wd_cross_fold after the dX dgrad). The (2L+1) align8(d) parameters are the
+    # dense layout's entry "cross" directly behind W1, trained by the dense Adam. Collective transport only,
+    # 1 <= L <= 4, emb_dim in [1, 64], d <= ops.CROSS_MAX_D. 0: the layout and the step are Wide&Deep's.
+    cross_layers: int = 0
 
     def __post_init__(self):
         if self.transport == "auto":
@@ -92,6 +99,19 @@ class WideDeepConfig:
                              "transport)")
         if self.fm_term and not 1 <= self.emb_dim <= 64:
             raise ValueError(f"fm_term: emb_dim is {self.emb_dim}, expected 1 <= emb_dim <= 64")
+        L = self.cross_layers
+        if isinstance(L, bool) or not isinstance(L, int) or not 0 <= L <= ops.CROSS_MAX_L:
+            raise ValueError(f"cross_layers is {L!r}, expected an int in [0, {ops.CROSS_MAX_L}]")
+        if L:
+            if "onesided" in (self.transport, self.dense_transport):
+                raise ValueError("cross_layers needs transport 'collective' (the cross layers are not built for the "
+                                 "one-sided transport)")
+            if not 1 <= self.emb_dim <= 64:
+                raise ValueError(f"cross_layers: emb_dim is {self.emb_dim}, expected 1 <= emb_dim <= 64")
+            d = self.F * self.emb_dim + self.n_dense
+            if d > ops.CROSS_MAX_D:
+                raise ValueError(f"cross_layers: the input has d = {d} columns, the kernels take d <= "
+                                 f"{ops.CROSS_MAX_D}")
 
     @property
     def F(self):
@@ -224,6 +244,12 @@ class WideDeep(LookaheadPlans):
         for i, n_out in enumerate(cfg.hidden):
             self.layout[f"W{i + 1}"] = (off, (n_out, self.k_pad[i]))
             off += _align(n_out * self.k_pad[i], 64)
+            if i == 0 and cfg.cross_layers:
+                # the cross parameters [w_0, b_0, ..., w_{L-1}, b_{L-1}, w_c] x align8(d), directly behind W1: inside
+                # layer 1's bucket, the last to go out -- _bucket_done(1, ...) releases the later buckets before the
+                # cross gradient (written after the dX dgrad) exists
+                self.layout["cross"] = (off, (2 * cfg.cross_layers + 1, _align(self.k_in[0])))
+                off += _align((2 * cfg.cross_layers + 1) * _align(self.k_in[0]), 64)
             if i > 0:
                 self.layout[f"b{i + 1}"] = (off, (n_out,))
                 off += _align(n_out, 64)
@@ -252,6 +278,9 @@ class WideDeep(LookaheadPlans):
             w[:, self.k_in[i]:] = 0  # bias column and padding start at zero
         h = self.cfg.hidden[-1]
         ops.kaiming_uniform_(self.view(full, "w4")[:h], h, g)
+        if self.cfg.cross_layers:  # drawn after the existing parameters: those keep their values; b_l = 0
+            d = self.k_in[0]
+            ops.kaiming_uniform_(self.view(full, "cross")[0::2, :d], d, g)
         return full.to(dev)
 
     def view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
@@ -292,7 +321,22 @@ class WideDeep(LookaheadPlans):
             )
             if cfg.fm_term:  # the per-sample column sums of the embeddings, kept for the backward
                 self._bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
+            if cfg.cross_layers:  # the cross layers' dot products and constants, and the partial batch sums
+                self._bufs[B].update(self._cross_buffers(B, part=True))
         return self._bufs[B]
+
+    def _cross_buffers(self, B, part=False):
+        L, dev = self.cfg.cross_layers, self.comm.device
+        bufs = dict(p=torch.empty(B, L + 1, dtype=torch.float32, device=dev),
+                    k=torch.empty(L + 1, dtype=torch.float32, device=dev))
+        if part:
+            bufs["part"] = torch.empty(ops.wd_cross_part_shape(B, self.k_in[0], L), dtype=torch.float32, device=dev)
+        return bufs
+
+    def _cross_forward(self, b, P):
+        """wide += the cross layers' output over the assembled X (after the DeepFM term, before the head)."""
+        ops.wd_cross_forward(b["X"], self.k_in[0], self.view(P, "cross"), self.cfg.cross_layers, b["wide"], b["p"],
+                             b["k"])
 
     def _forward(self, b, P):
         ops.linear_fwd(b["X"], self.view(P, "W1"), None, "relu", out=b["H1"])
@@ -311,6 +355,8 @@ class WideDeep(LookaheadPlans):
         ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
         if self.cfg.fm_term:
             ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
+        if self.cfg.cross_layers:
+            self._cross_forward(b, P)
         self._forward(b, P)
         h = self.cfg.hidden[-1]
         w4 = self.view(P, "w4").float()
@@ -329,6 +375,8 @@ class WideDeep(LookaheadPlans):
                            **{f"H{i + 1}": torch.empty(B, n, **bf) for i, n in enumerate(cfg.hidden)})
             if cfg.fm_term:
                 bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
+            if cfg.cross_layers:
+                bufs[B].update(self._cross_buffers(B))
         return bufs[B]
 
     def evaluate(self, batches, evaluator=None) -> dict:
@@ -359,6 +407,8 @@ class WideDeep(LookaheadPlans):
             ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
             if cfg.fm_term:
                 ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
+            if cfg.cross_layers:
+                self._cross_forward(b, P)
             self._forward(b, P)
             ev.update_head(b["H3"], w4[:h], w4[h:h + 1], b["wide"], labels)
         ev.reduce(self.comm)
@@ -419,6 +469,8 @@ class WideDeep(LookaheadPlans):
         P = self.dense.get()
         scale = 1.0 / (B * self.comm.world)
         w4, gw4 = self.view(P, "w4"), self.view(G, "w4")
+        if cfg.cross_layers:  # DCN: wide += <x_L, w_c>; it reads the pulled values, so behind the Adam wait above
+            self._cross_forward(b, P)
         sink = self.dense.slab_sink() if hasattr(self.dense, "slab_sink") else None
         side = self._side
         defer = _HEAD_DEFER and side.stream is not None
@@ -458,9 +510,20 @@ class WideDeep(LookaheadPlans):
         else:
             ops.linear_dgrad(b["dH1"], self.view(P, "W1"), n_cols=F * D, out=b["dX"])
         # W's last reader of the step is issued: a side-stream dense Adam may start after this point
-        w_read = side.point() if _ADAM_AFTER_DGRAD and self.comm.world == 1 else None
+        adam_point = _ADAM_AFTER_DGRAD and self.comm.world == 1
+        w_read = side.point() if adam_point and not cfg.cross_layers else None
         if cfg.fm_term:  # DeepFM: dX += dz (S - v) per lookup, in the order the dgrad wrote the rows
             ops.wd_fm_backward(b["X"], b["S"], b["dwide"], b["dX"], F, D, perm=plan.csr[2] if sorted_rows else None)
+        if cfg.cross_layers:
+            # DCN: dX += sum_j m_j w_j per lookup, the per-chunk batch sums, then the cross gradients into G
+            Pc = self.view(P, "cross")
+            ops.wd_cross_backward(b["X"], self.k_in[0], b["p"], b["k"], b["dwide"], Pc, cfg.cross_layers, b["dX"], F, D,
+                                  b["part"], perm=plan.csr[2] if sorted_rows else None)
+            ops.wd_cross_fold(b["part"], Pc, self.k_in[0], cfg.cross_layers, self.view(G, "cross"))
+            # the side-stream Adam rewrites the pulled values and clears G: the cross backward still reads the
+            # former and the fold writes the latter, so here the point the Adam waits for lies behind the fold, not
+            # behind the dX dgrad (DeepFM's term touches neither and may stay behind the point)
+            w_read = side.point() if adam_point else None
         if _W1_LATE:  # the layer-1 weight gradient beside the memory-bound embedding backward instead
             with side.fork():
                 _wgrad(b["dH1"], b["X"], self.view(G, "W1"), sink)

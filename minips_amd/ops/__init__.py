@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import dfmk, evalk, fmk, ftrlk, kernels, optk, wdftrlk
+from .._native import dcnk, dfmk, evalk, fmk, ftrlk, kernels, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -750,6 +750,167 @@ def wd_fm_backward(X, S, dwide, dX, F, D, perm=None, blocks=0):
     r = r[ok]
     dx[r] = (dx[r].float() + dz[ok] * (Sb[ok] - v[ok])).to(torch.bfloat16)
     return dX
+
+
+# ----------------------------------------------------------------------------- Deep & Cross layers
+CROSS_MAX_D = 2048   # csrc/kernels/dcn.h: kDcnMaxD, kDcnMaxL, kDcnChunk, kDcnTrailer (the binding exports them too)
+CROSS_MAX_L = 4
+CROSS_CHUNK = 32
+CROSS_TRAILER = 8
+
+
+def wd_cross_part_shape(B, d, L):
+    """Shape of wd_cross_backward's per-chunk partial batch sums: one row per CROSS_CHUNK samples holding the L+1
+    partial T_j rows of align8(d) columns and a trailer whose first L+1 slots are the partial scalar sums."""
+    return (int(B) + CROSS_CHUNK - 1) // CROSS_CHUNK, (int(L) + 1) * ((int(d) + 7) // 8 * 8) + CROSS_TRAILER
+
+
+def _wd_cross_check(X, d, Pc, L):
+    if not 1 <= L <= CROSS_MAX_L:
+        raise RuntimeError(f"wd_cross: L is {L}, expected 1 <= L <= {CROSS_MAX_L}")
+    if not 1 <= d <= CROSS_MAX_D:
+        raise RuntimeError(f"wd_cross: d is {d}, expected 1 <= d <= {CROSS_MAX_D}")
+    if X is not None and (X.dim() != 2 or X.shape[1] < d):
+        raise RuntimeError(f"wd_cross: X has shape {tuple(X.shape)}, expected [B, >= d = {d}]")
+    if tuple(Pc.shape) != (2 * L + 1, (d + 7) // 8 * 8):
+        raise RuntimeError(f"wd_cross: Pc has shape {tuple(Pc.shape)}, expected [{2 * L + 1}, {(d + 7) // 8 * 8}]")
+
+
+def _wd_cross_a(p, k, L):
+    """a_0 .. a_L of the scalar rule (csrc/kernels/dcn.h), one rounded fp32 operation per line."""
+    a = [torch.ones_like(p[:, 0])]
+    for l in range(L):
+        t = a[l] * p[:, l]
+        s = t + k[l]
+        a.append(a[l] + s)
+    return a
+
+
+def wd_cross_forward(X, d, Pc, L, wide, p=None, k=None, blocks=0):
+    """Deep & Cross layers over the assembled Wide&Deep input (the rule: csrc/kernels/dcn.h). X bf16 [B, >= d],
+    x_0 = X[:, :d]; Pc bf16 [(2L+1), align8(d)] holds w_0, b_0, ..., w_{L-1}, b_{L-1}, w_c. With p_j = <x_0, w_j>
+    and k_j = <b_0 + ... + b_{j-1}, w_j> (w_L = w_c):  a = 1; s_l = a p_l + k_l; a += s_l (l < L);
+    wide[b] += a p_L + k_L -- the recurrence x_{l+1} = x_0 <x_l, w_l> + b_l + x_l, wide += <x_L, w_c>, exactly.
+    Returns (p fp32 [B, L+1], k fp32 [L+1]) for the backward (written in place when given, no allocation). Columns
+    >= d of X and of Pc are never read. ``blocks`` > 0 forces the GPU grid size. One gfx950 launch on the GPU (one
+    wave per sample, no atomics, the same bits for every grid size); the CPU path is the fp32 PyTorch reference of
+    the same rule (its dot products are summed in PyTorch's order)."""
+    d, L, B = int(d), int(L), X.shape[0]
+    if p is None:
+        p = torch.empty(B, L + 1, dtype=torch.float32, device=X.device)
+    if k is None:
+        k = torch.empty(L + 1, dtype=torch.float32, device=X.device)
+    if _gpu(X):
+        dcnk().wd_cross_forward(X, d, Pc, L, wide, p, k, int(blocks))
+        return p, k
+    _wd_cross_check(X, d, Pc, L)
+    if B == 0:
+        return p, k
+    x = X[:, :d].float()
+    W, bb = Pc[0::2, :d].float(), Pc[1::2, :d].float()
+    p.copy_(x @ W.t())
+    Bj = torch.cat([torch.zeros(1, d), torch.cumsum(bb, 0)])  # B_0 .. B_L
+    k.copy_((Bj * W).sum(1))
+    a = _wd_cross_a(p, k, L)
+    t = a[L] * p[:, L]
+    wide += t + k[L]
+    return p, k
+
+
+def wd_cross_backward(X, d, p, k, dwide, Pc, L, dX, F, D, part, perm=None, blocks=0):
+    """The cross layers' backward (csrc/kernels/dcn.h) from the forward's ``p`` and ``k``: nothing is recomputed
+    over d. Per sample dz = dwide[b], ds_L = dz, r = dz p_L, ds_l = r, r += ds_l p_l (l = L-1 .. 0), m_j = ds_j a_j.
+    Embedding gradient: for every lookup (b, f), row r = perm[b*F + f] (b*F + f without ``perm``) of ``dX`` (bf16,
+    B*F*D contiguous elements) viewed as [B*F, D] becomes bf16(dX[r].float() + sum_j m_j w_j[f*D:(f+1)*D]), the sum
+    in the order j = 0 .. L; a ``perm`` (int32) entry outside [0, B*F) is skipped, the dense-feature columns get no
+    gradient. Batch sums: ``part`` (fp32, wd_cross_part_shape) receives per chunk of CROSS_CHUNK samples the partial
+    T_j = sum_b m_j x_0 and sum_b ds_j for ops.wd_cross_fold. In place; the CPU path computes the same dX bits."""
+    d, L, F, D, B = int(d), int(L), int(F), int(D), X.shape[0]
+    if _gpu(X):
+        dcnk().wd_cross_backward(X, d, p, k, dwide, Pc, L, perm, dX, F, D, part, int(blocks))
+        return dX
+    _wd_cross_check(X, d, Pc, L)
+    if not 1 <= D <= 64 or F < 1 or F * D > d:
+        raise RuntimeError(f"wd_cross_backward: D is {D} and F is {F}, expected 1 <= D <= 64, F >= 1, F * D <= d")
+    n = B * F
+    if dX.numel() != n * D or not dX.is_contiguous():
+        raise RuntimeError(f"wd_cross_backward: dX {tuple(dX.shape)}, expected {n * D} contiguous elements")
+    if tuple(part.shape) != wd_cross_part_shape(B, d, L):
+        raise RuntimeError(f"wd_cross_backward: part {tuple(part.shape)}, expected {wd_cross_part_shape(B, d, L)}")
+    if B == 0:
+        return dX
+    L1, dp = L + 1, (d + 7) // 8 * 8
+    x = X[:, :d].float()
+    W = Pc[0::2, :d].float()
+    a = _wd_cross_a(p, k, L)
+    ds = [None] * L1
+    ds[L] = dwide
+    r = dwide * p[:, L]
+    for l in range(L - 1, -1, -1):
+        ds[l] = r
+        t = ds[l] * p[:, l]
+        r = r + t
+    m = torch.stack([ds[j] * a[j] for j in range(L1)], 1)  # [B, L+1]
+    ds = torch.stack(ds, 1)
+    g = m[:, 0:1] * W[0, : F * D]
+    for j in range(1, L1):
+        t = m[:, j: j + 1] * W[j, : F * D]
+        g = g + t
+    g = g.reshape(n, D)
+    dx = dX.view(n, D)
+    if perm is None:
+        dx.copy_((dx.float() + g).to(torch.bfloat16))
+    else:
+        r = perm.long()
+        ok = (r >= 0) & (r < n)
+        r = r[ok]
+        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
+    nch = part.shape[0]
+    pad = nch * CROSS_CHUNK - B
+    mc = torch.cat([m, m.new_zeros(pad, L1)]).view(nch, CROSS_CHUNK, L1)
+    xc = torch.cat([x, x.new_zeros(pad, d)]).view(nch, CROSS_CHUNK, d)
+    part.zero_()
+    part[:, : L1 * dp].view(nch, L1, dp)[:, :, :d] = torch.einsum("cbj,cbd->cjd", mc, xc)
+    part[:, L1 * dp: L1 * dp + L1] = torch.cat([ds, ds.new_zeros(pad, L1)]).view(nch, CROSS_CHUNK, L1).sum(1)
+    return dX
+
+
+def wd_cross_fold(part, Pc, d, L, Gc):
+    """The cross parameters' gradients from the backward's partial batch sums, ADDED into ``Gc`` (fp32
+    [(2L+1), align8(d)], rows as Pc's): with T_j and Sd_j the sums of the chunks in chunk order and B_l = b_0 + ...
+    + b_{l-1}:  dw_l = T_l + B_l Sd_l (l = 0 .. L, w_L = w_c),  db_l = Sd_L w_c + sum_{j>l} Sd_j w_j (added in the
+    order j = L-1 .. l+1). One gfx950 launch; the CPU path is the fp32 reference of the same rule."""
+    d, L = int(d), int(L)
+    nch = part.shape[0]
+    if _gpu(part):
+        dcnk().wd_cross_fold(part, nch, Pc, d, L, Gc)
+        return Gc
+    _wd_cross_check(None, d, Pc, L)
+    L1, dp = L + 1, (d + 7) // 8 * 8
+    if part.dim() != 2 or part.shape[1] != L1 * dp + CROSS_TRAILER or tuple(Gc.shape) != (2 * L + 1, dp):
+        raise RuntimeError(f"wd_cross_fold: part {tuple(part.shape)} / Gc {tuple(Gc.shape)}, expected "
+                           f"[nchunks, {L1 * dp + CROSS_TRAILER}] / [{2 * L + 1}, {dp}]")
+    if nch == 0:
+        return Gc
+    T = part[:, : L1 * dp].view(nch, L1, dp)[:, :, :d]
+    S = part[:, L1 * dp: L1 * dp + L1]
+    Tt, Sd = torch.zeros(L1, d), torch.zeros(L1)
+    for c in range(nch):
+        Tt = Tt + T[c]
+        Sd = Sd + S[c]
+    W, bb = Pc[0::2, :d].float(), Pc[1::2, :d].float()
+    Bc = torch.zeros(d)
+    for l in range(L1):
+        t = Bc * Sd[l]
+        Gc[2 * l, :d] += Tt[l] + t
+        if l < L:
+            Bc = Bc + bb[l]
+    r = Sd[L] * W[L]
+    for l in range(L - 1, -1, -1):
+        Gc[2 * l + 1, :d] += r
+        t = Sd[l] * W[l]
+        r = r + t
+    return Gc
 
 
 # ----------------------------------------------------------------------------- held-out evaluation

@@ -10,6 +10,8 @@ num_iters (= --steps), alpha (LR). Extra: --fail_rank/--fail_step fault injectio
 --eval_every/--eval_batches/--eval_seed (held-out AUC and log loss of widedeep / dlrm; off by default).
 --model deepfm is widedeep with the FM second-order term over its field embeddings (WideDeepConfig(fm_term=True)):
 every widedeep flag applies, the final JSON gains fm_term, SSP / ASP need --transport collective.
+--model dcn is widedeep with --cross_layers (default 3, 1..4) Deep & Cross layers over its whole input
+(WideDeepConfig(cross_layers=L)): every widedeep flag applies, the final JSON gains cross_layers, collective only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -35,7 +37,7 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm"])
+                                                             "deepfm", "dcn"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -127,6 +129,8 @@ def parse(argv=None):
                     help="--wide_optimizer ftrl: factor on the pushed mean-loss gradient of the wide columns; 0 "
                          "(default): batch size x world, the summed-loss gradient")
     ap.add_argument("--fm_k", type=int, default=16, help="fm: factors per feature (k % 4 == 0, 4 <= k <= 60)")
+    ap.add_argument("--cross_layers", type=int, default=None,
+                    help="dcn: cross layers over the assembled input, 1..4 (default 3)")
     ap.add_argument("--fm_fields", type=int, default=0,
                     help="fm, synthetic data: fields per sample, one active feature each (0: 8 with --small, else 64)")
     ap.add_argument("--fm_card", type=int, default=0,
@@ -142,8 +146,8 @@ def parse(argv=None):
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     if args.wide_optimizer == "ftrl":
-        if args.model not in ("widedeep", "deepfm", "fm"):
-            ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm and fm, not {args.model}")
+        if args.model not in ("widedeep", "deepfm", "dcn", "fm"):
+            ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm, dcn and fm, not {args.model}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
         if not 0 <= args.ftrl_grad_scale < float("inf"):
@@ -159,8 +163,8 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dlrm", "fm"):
-        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dlrm and fm, not "
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm and fm, not "
                  f"{args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
@@ -174,11 +178,21 @@ def parse(argv=None):
         if args.eval_every > 0 and args.input:
             ap.error("--model fm: --eval_every needs the synthetic stream (an --input file has no held-out split)")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
-        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm")
+        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm", "dcn")
                           and args.consistency in ("ssp", "asp") else "collective")
     if args.model == "deepfm" and args.transport == "onesided":
         ap.error("--model deepfm with SSP / ASP needs --transport collective (the FM term is not built for the "
                  "one-sided transport)")
+    if args.cross_layers is not None and args.model != "dcn":
+        ap.error(f"--cross_layers: --model dcn only, not {args.model}")
+    if args.model == "dcn":
+        if args.cross_layers is None:
+            args.cross_layers = 3
+        if not 1 <= args.cross_layers <= 4:
+            ap.error(f"--model dcn: --cross_layers {args.cross_layers} must be in [1, 4]")
+        if args.transport == "onesided":
+            ap.error("--model dcn with SSP / ASP needs --transport collective (the cross layers are not built for the "
+                     "one-sided transport)")
     if args.wide_optimizer == "ftrl" and args.transport == "onesided":
         ap.error("--wide_optimizer ftrl with SSP / ASP needs --transport collective (the one-sided owners apply the "
                  "row-wise Adagrad only)")
@@ -252,7 +266,7 @@ def build(args, comm):
     dev = comm.device
     r = comm.rank
     seed = args.seed * 1000 + r
-    if args.model in ("widedeep", "deepfm"):  # deepfm: the same model with the FM term over its embeddings
+    if args.model in ("widedeep", "deepfm", "dcn"):  # deepfm / dcn: the same model with the FM term / cross layers
         from .data.synthetic import CriteoSynth
         from .models.widedeep import WideDeep, WideDeepConfig
 
@@ -264,6 +278,7 @@ def build(args, comm):
                         wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
         cfg = WideDeepConfig(consistency=args.consistency, staleness=args.staleness, transport=args.transport,
                              max_batch=B, fm_term=args.model == "deepfm",
+                             cross_layers=args.cross_layers if args.model == "dcn" else 0,
                              **({"cards": SMALL_CARDS} if args.small else {}), **wide)
         m = WideDeep(cfg, comm)
         return m, {0: m.emb, 1: m.dense}, (lambda: CriteoSynth(B, cards=cfg.cards, device=dev, seed=seed)), \
@@ -818,6 +833,8 @@ def main(argv=None):
         ftrl_final = dict(wide_nnz=model.wide_nnz(), wide_optimizer="ftrl")
     if args.model == "deepfm":
         ftrl_final["fm_term"] = True
+    if args.model == "dcn":
+        ftrl_final["cross_layers"] = args.cross_layers
     clip_final = {}
     if args.clip_norm:
         cs = tables[0].clip_stats()

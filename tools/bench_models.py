@@ -10,7 +10,8 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         dlrm-10b (config 5 at its per-GPU shard: 1.25B rows x 64 bf16 per GPU, ASP), lr (config 1 on GPUs,
         samples/s), kmeans (samples/s), widedeep-ssp (config 3), widedeep (the same driver under BSP; takes
         --wide_optimizer ftrl and reports wide_nnz), deepfm (widedeep with the FM term over its embeddings,
-        WideDeepConfig(fm_term=True)).
+        WideDeepConfig(fm_term=True)), dcn (widedeep with --cross_layers Deep & Cross layers over its input,
+        WideDeepConfig(cross_layers=L)).
 """
 from __future__ import annotations
 
@@ -135,20 +136,21 @@ def build(args, comm):
         g.manual_seed(r)
         return m, (lambda: m.train_step(torch.randn(B, cfg.dims, generator=g, device=dev))), B, "samples/s", \
             dict(model="mini-batch K-Means K=1000 D=128", seq_len=None)
-    if args.model in ("widedeep", "widedeep-ssp", "deepfm"):
+    if args.model in ("widedeep", "widedeep-ssp", "deepfm", "dcn"):
         from minips_amd.data.synthetic import CriteoSynth
         from minips_amd.models.widedeep import WideDeep, WideDeepConfig
 
         B = args.batch or 16384
-        bsp = args.model in ("widedeep", "deepfm")
+        bsp = args.model in ("widedeep", "deepfm", "dcn")
         fm_term = args.model == "deepfm"
+        cross = args.cross_layers if args.model == "dcn" else 0
         wide = {}
         if args.wide_optimizer == "ftrl":
             wide = dict(wide_optimizer="ftrl", wide_alpha=args.ftrl_alpha, wide_beta=args.ftrl_beta,
                         wide_l1=args.ftrl_l1, wide_l2=args.ftrl_l2,
                         wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
         cfg = WideDeepConfig(consistency="bsp" if bsp else "ssp", staleness=0 if bsp else max(1, args.staleness),
-                             transport=args.transport, max_batch=B, fm_term=fm_term, **wide)
+                             transport=args.transport, max_batch=B, fm_term=fm_term, cross_layers=cross, **wide)
         m = WideDeep(cfg, comm)
         if bsp:  # BSP, the look-ahead feeder below
             from minips_amd.models.feeder import LookaheadFeeder
@@ -163,7 +165,10 @@ def build(args, comm):
             extra = dict(wide_optimizer="ftrl", ftrl=wide) if wide else {}
             if fm_term:
                 extra["fm_term"] = True
-            name = "DeepFM (Wide&Deep + FM term)" if fm_term else "Wide&Deep"
+            if cross:
+                extra["cross_layers"] = cross
+            name = ("DeepFM (Wide&Deep + FM term)" if fm_term else
+                    f"DCN (Wide&Deep + {cross} cross layers)" if cross else "Wide&Deep")
             return m, feeder.step, B, "samples/s", dict(model=f"{name} Criteo BSP (collective)", seq_len=None,
                                                  consistency="bsp", transport=args.transport, feeder="lookahead",
                                                  **extra)
@@ -198,7 +203,7 @@ def build(args, comm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
-                                                         "widedeep-ssp", "widedeep", "fm", "deepfm"])
+                                                         "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -233,9 +238,12 @@ def main():
                          "gains wide_nnz)")
     ap.add_argument("--ftrl_grad_scale", type=float, default=0.0, help="widedeep ftrl: 0 = batch size x world")
     ap.add_argument("--fm_k", "--fm-k", dest="fm_k", type=int, default=16, help="fm: factors per feature")
+    ap.add_argument("--cross_layers", type=int, default=3, help="dcn: cross layers, 1..4")
     args = ap.parse_args()
-    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "fm"):
-        ap.error("--wide_optimizer ftrl: --model widedeep, deepfm and fm only")
+    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "fm"):
+        ap.error("--wide_optimizer ftrl: --model widedeep, deepfm, dcn and fm only")
+    if args.model == "dcn" and not 1 <= args.cross_layers <= 4:
+        ap.error("--model dcn: --cross_layers must be in [1, 4]")
     if args.sparse_optimizer == "ftrl" and (args.model != "lr" or args.value_dtype != "float32"):
         ap.error("--sparse_optimizer ftrl: --model lr with --value-dtype float32 only")
     if args.clip_norm and args.model != "gpt2":
@@ -276,7 +284,8 @@ def main():
             "value": round(per_step * comm.world * args.steps / el, 1), "unit": unit, "n_gpus": comm.world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * el / args.steps, 3),
             "higher_is_better": True, "scaling": "weak",
-            "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp", "widedeep", "deepfm")
+            "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp", "widedeep", "deepfm",
+                                                 "dcn")
                       else ("fp64" if args.value_dtype == "float64" and args.model == "lr" else "fp32")),
             "data": "synthetic", "last": float(out.float().sum()) if torch.is_tensor(out) else None,
             "config": dict(cfg, parallelism=f"ps-dp{comm.world}"),

@@ -21,6 +21,8 @@ Targets
             backward: a sixth small torch extension, over k_fm.o only)
   deepfm_py csrc/bindings/deepfm_py.cpp  -> minips_amd/_dfmk*.so     (DeepFM's FM interaction term on the Wide & Deep
             input: a seventh small torch extension, over k_deepfm.o only)
+  dcn_py    csrc/bindings/dcn_py.cpp     -> minips_amd/_dcnk*.so     (the Deep & Cross layers on the Wide & Deep
+            input: an eighth small torch extension, over k_dcn.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -254,6 +256,11 @@ def build_deepfm_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "deepfm_py", "_dfmk", "k_deepfm.o")
 
 
+def build_dcn_py(kobjs: list[str]) -> str:
+    """minips_amd/_dcnk: the Deep & Cross binding over k_dcn.o alone."""
+    return _build_small_ext(kobjs, "dcn_py", "_dcnk", "k_dcn.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -281,7 +288,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 def main(argv: list[str]) -> int:
     targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
-                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py"}
+                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -297,7 +304,7 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py"}:
+    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -314,6 +321,8 @@ def main(argv: list[str]) -> int:
             print("built", build_fm_py(kobjs))
         if targets & {"kernels", "deepfm_py"}:
             print("built", build_deepfm_py(kobjs))
+        if targets & {"kernels", "dcn_py"}:
+            print("built", build_dcn_py(kobjs))
     return 0
 
 
