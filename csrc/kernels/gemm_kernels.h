@@ -140,6 +140,17 @@ __device__ __forceinline__ int64_t out_offset(const EpiArgs& ep, int N, int row,
   return (int64_t)row * ep.ldc + col;
 }
 
+// gelu'(u) of the tanh form for kEpiGeluGradBf16, where it scales an accumulator: 0.5 (1 + t) + 0.5 u (1 - t^2) ...
+// cancels at t -> -1 (t rounds to -1 from u ~ -5.2 on and the product becomes 0; an absolute error near 1e-6 times
+// |acc|). With z = k (u + c3 u^3): (1 + t) / 2 = sigmoid(2z) = s and 1 - t^2 = 4 s (1 - s), and from e = exp(-2|z|),
+// r = 1 / (1 + e) both s (r or e r) and s (1 - s) = e r^2 come without a subtraction: a few ulp relative.
+__device__ __forceinline__ float gelu_grad_stable(float u) {
+  const float k = 0.7978845608f, c3 = 0.044715f;
+  const float z = k * (u + c3 * u * u * u);
+  const float e = expf(-2.f * fabsf(z)), r = 1.f / (1.f + e);
+  return (z >= 0.f ? r : e * r) + 2.f * u * (e * r * r) * k * (1.f + 3.f * c3 * u * u);
+}
+
 // Fused epilogue of one wave's (16 MR) x 64 accumulator block at rows mb.., cols nb...
 template <int EPI, int MR>
 __device__ __forceinline__ void epilogue_at(const v4f (&acc)[MR][4], const EpiArgs& ep, int M, int N, int mb, int nb,
@@ -194,10 +205,7 @@ __device__ __forceinline__ void epilogue_at(const v4f (&acc)[MR][4], const EpiAr
           ((bf16_t*)ep.C)[off] = f2bf(v * bf2f(ep.mask[(int64_t)row * ep.ldmask + col]));
         } else if (EPI == kEpiGeluGradBf16) {
           const float u = bf2f(ep.mask[(int64_t)row * ep.ldmask + col]);
-          const float k = 0.7978845608f, c3 = 0.044715f;
-          const float t = tanhf(k * (u + c3 * u * u * u));
-          const float gp = 0.5f * (1.f + t) + 0.5f * u * (1.f - t * t) * k * (1.f + 3.f * c3 * u * u);
-          ((bf16_t*)ep.C)[off] = f2bf(v * gp);
+          ((bf16_t*)ep.C)[off] = f2bf(v * gelu_grad_stable(u));
         } else if (EPI == kEpiReluMaskBf16) {
           float m = bf2f(ep.mask[(int64_t)row * ep.ldmask + col]);
           float o = m > 0.f ? v : 0.f;
@@ -242,12 +250,7 @@ __device__ __forceinline__ float epi_apply(float v, float bias, float m, bf16_t*
     return 0.5f * x * (1.f + t);
   }
   if (EPI == kEpiMulAuxBf16) return v * m;
-  if (EPI == kEpiGeluGradBf16) {
-    const float k = 0.7978845608f, c3 = 0.044715f;
-    const float t = tanhf(k * (m + c3 * m * m * m));
-    const float gp = 0.5f * (1.f + t) + 0.5f * m * (1.f - t * t) * k * (1.f + 3.f * c3 * m * m);
-    return v * gp;
-  }
+  if (EPI == kEpiGeluGradBf16) return v * gelu_grad_stable(m);
   if (EPI == kEpiReluMaskBf16) return m > 0.f ? v : 0.f;
   return v;  // kEpiStoreBf16 / kEpiPermRowsBf16 / kEpiStoreF32
 }

@@ -31,9 +31,13 @@ _L2E = 1.4426950408889634
 
 
 def _gelu_grad(u):
+    # with s = sigmoid(2z) = (1 + t) / 2 and 1 - t^2 = 4 s (1 - s): from e = exp(-2|z|) and r = 1 / (1 + e), without
+    # the cancellation of 1 + t at t -> -1 (gemm_kernels.h gelu_grad_stable)
     k, c = 0.7978845608, 0.044715
-    t = torch.tanh(k * (u + c * u ** 3))
-    return 0.5 * (1 + t) + 0.5 * u * (1 - t * t) * k * (1 + 3 * c * u * u)
+    z = k * (u + c * u ** 3)
+    e = torch.exp(-2 * z.abs())
+    r = 1 / (1 + e)
+    return torch.where(z >= 0, r, e * r) + 2 * u * (e * r * r) * k * (1 + 3 * c * u * u)
 
 
 def _gpu(t: torch.Tensor) -> bool:
@@ -123,14 +127,15 @@ def gemm(A, B, C, M, N, K, a_km=False, b_kn=False, epi=EPI_STORE_F32, bias=None,
     return C
 
 
-def gemm_batched(A, B, C, M, N, K, a_km, b_kn, epi, batch, inner, lda, ldb, ldc, strides, alpha=1.0, bias=None):
+def gemm_batched(A, B, C, M, N, K, a_km, b_kn, epi, batch, inner, lda, ldb, ldc, strides, alpha=1.0, bias=None,
+                 tile=0):
     """``batch`` GEMMs over flat buffers; operand z starts at (z//inner)*s_outer + (z%inner)*s_inner
-    (strides = [sa_o, sa_i, sb_o, sb_i, sc_o, sc_i] in elements), leading dims lda/ldb/ldc."""
+    (strides = [sa_o, sa_i, sb_o, sb_i, sc_o, sc_i] in elements), leading dims lda/ldb/ldc. ``tile``: gemm's."""
     if _gpu(A):
         if _REC is not None:
             raise RuntimeError("ops.recording: batched GEMMs are not recordable")
         kernels().gemm(A, B, C, M, N, K, a_km, b_kn, epi, bias, None, None, float(alpha), 1, int(batch), int(inner),
-                       int(lda), int(ldb), int(ldc), [int(x) for x in strides])
+                       int(lda), int(ldb), int(ldc), [int(x) for x in strides], None, 0, int(tile))
         return C
     Af, Bf, Cf = A.reshape(-1), B.reshape(-1), C.reshape(-1)
     for z in range(batch):
