@@ -20,6 +20,8 @@
   ``ops.wd_fm_backward``): a seventh small torch extension, same rule.
 * ``_dcnk``     -- the Deep & Cross layers over the assembled Wide & Deep input (``ops.wd_cross_forward`` /
   ``ops.wd_cross_backward`` / ``ops.wd_cross_fold``): an eighth small torch extension, same rule.
+* ``_ffmk``     -- the field-aware factorization-machine forward and backward over a CSR batch of pulled rows
+  (``ops.ffm_forward`` / ``ops.ffm_backward``): a ninth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -95,6 +97,11 @@ def dcnk():
     return _load("_dcnk", "gfx950 HIP Deep & Cross kernels")
 
 
+def ffmk():
+    """Return the HIP field-aware factorization-machine kernel module or raise a loud error."""
+    return _load("_ffmk", "gfx950 HIP field-aware factorization-machine kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -130,6 +137,10 @@ def dfmk_available() -> bool:
 
 def dcnk_available() -> bool:
     return _available(dcnk)
+
+
+def ffmk_available() -> bool:
+    return _available(ffmk)
 
 
 def native_dir() -> str:

@@ -238,3 +238,30 @@ class FMSynth:
         rowptr = torch.arange(0, (B + 1) * F, F, device=self.device, dtype=torch.int64)
         vals = torch.ones(B * F, dtype=torch.float32, device=self.device)
         return rowptr, cols.reshape(-1), vals, y
+
+
+class FFMSynth(FMSynth):
+    """FMSynth's batches with a field-aware teacher (the rule of csrc/kernels/ffm.h): feature u keeps one vector
+    per partner field, V [num_dims, fields, k_teacher] ~ N(0, 1), w ~ N(0, 0.3^2), and
+    z* = sum_f w_{c_f} + sum_{f<g} <V[c_f, g], V[c_g, f]> over the one active feature c_f = f * card + id of every
+    field. next() returns (rowptr, cols, vals, labels); a key's field is key // card."""
+
+    def __init__(self, batch: int, fields: int = 8, card: int = 32, k_teacher: int = 4, device="cpu", seed: int = 0):
+        super().__init__(batch, fields, card, k_teacher, device, seed)
+        g = torch.Generator(device="cpu")  # the teacher is the same on every device
+        g.manual_seed(seed)
+        self.v = torch.randn(self.num_dims, fields, k_teacher, generator=g).to(self.device)
+        self.w = (0.3 * torch.randn(self.num_dims, generator=g)).to(self.device)
+        self.upper = torch.triu(torch.ones(fields, fields, device=self.device), diagonal=1)
+
+    def holdout(self, seed: int) -> "FFMSynth":
+        g = FFMSynth.__new__(FFMSynth)
+        g.__dict__.update(self.__dict__)
+        g.gen = torch.Generator(device=self.device)
+        g.gen.manual_seed(seed)
+        return g
+
+    def teacher_logits(self, cols2d: torch.Tensor) -> torch.Tensor:
+        a = self.v[cols2d]  # [B, F, F, k]: a[b, f, g] = V[c_f, g]
+        pair = (a * a.transpose(1, 2)).sum(-1)
+        return self.w[cols2d].sum(1) + (pair * self.upper).sum((1, 2))

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import dcnk, dfmk, evalk, fmk, ftrlk, kernels, optk, wdftrlk
+from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, kernels, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1086,6 +1086,135 @@ def fm_backward(inv, rowid, vals, dz, S, rows, k, grad_rows, csr=None, blocks=0)
     touched = torch.zeros(rows.shape[0], dtype=torch.bool)
     touched[inv] = True
     grad_rows[: rows.shape[0]][touched] = acc[touched]
+    return grad_rows
+
+
+# ----------------------------------------------------------------------------- field-aware factorization machine
+FFM_MAX_F, FFM_MAX_K, FFM_MAX_FK = 64, 16, 512   # csrc/kernels/ffm.h (the binding exports them too)
+
+
+def _ffm_check(F: int, k: int, width: int):
+    if k % 4 or not 4 <= k <= FFM_MAX_K or not 1 <= F <= FFM_MAX_F or F * k > FFM_MAX_FK:
+        raise RuntimeError(f"ffm: F is {F} and k is {k}, expected k % 4 == 0, 4 <= k <= {FFM_MAX_K}, 1 <= F <= "
+                           f"{FFM_MAX_F} and F * k <= {FFM_MAX_FK}")
+    if width < F * k + 4:
+        raise RuntimeError(f"ffm: rows are {width} wide, expected >= F * k + 4 = {F * k + 4}")
+
+
+def _ffm_padded(rowptr, inv, vals, fields, cap, F):
+    """The batch padded to its max nnz: (pos [B, Mx] lookup index, ok [B, Mx] a lookup that counts, r / f / x
+    [B, Mx] its row, field and value (0 where not ok)) and rowid [n]. rowptr is clamped to [0, n]."""
+    B, n = rowptr.numel() - 1, inv.numel()
+    rp = rowptr.clamp(0, n)
+    st, cnt = rp[:-1], (rp[1:] - rp[:-1]).clamp(min=0)
+    Mx = int(cnt.max()) if B else 0
+    pos = st[:, None] + torch.arange(Mx, dtype=torch.int64)[None, :]
+    inside = torch.arange(Mx)[None, :] < cnt[:, None]
+    pos = torch.where(inside, pos, torch.zeros_like(pos))
+    r, f = inv[pos], fields[pos].long()
+    ok = inside & (r >= 0) & (r < cap) & (f >= 0) & (f < F)
+    zero = torch.zeros_like(pos)
+    x = torch.where(ok, vals.float()[pos], torch.zeros(()))
+    rowid = torch.repeat_interleave(torch.arange(B, dtype=torch.int64), cnt)
+    if rowid.numel() != n or int(st[0] if B else 0) != 0:  # a rowptr that does not cover [0, n)
+        full = torch.zeros(n, dtype=torch.int64)
+        full[pos[inside]] = torch.arange(B)[:, None].expand(B, Mx)[inside]
+        rowid = full
+    return pos, inside, ok, torch.where(ok, r, zero), torch.where(ok, f, zero), x, rowid
+
+
+def _ffm_chunks(B, Mx, k):
+    """Sample ranges whose [b, Mx, Mx, k] intermediates stay near 2^24 elements."""
+    step = max(1, (1 << 24) // max(1, Mx * Mx * k))
+    return [(lo, min(B, lo + step)) for lo in range(0, B, step)]
+
+
+def ffm_forward(rowptr, inv, vals, fields, labels, rows, F, k, w0=None, gscale=1.0, blocks=0):
+    """Field-aware factorization machine over a CSR batch of pulled rows [v_0 | v_1 | ... | v_{F-1} | w | pad]
+    (the rule: csrc/kernels/ffm.h): slot g (k columns) of a row is the vector its feature uses against a partner
+    of field g. Sample b holds the lookups j in [rowptr[b], rowptr[b+1]); lookup j reads rows[inv[j]] with value
+    vals[j] and field fields[j] (int32 in [0, F)). y = labels > 0.5. Returns fp32 (z [B], dz [B], loss [B]) and
+    rowid int32 [n]:
+      z = w0 + sum_j w x + sum_{i<j} <v_{inv[i], fields[j]}, v_{inv[j], fields[i]}> x_i x_j,
+      loss = max(z, 0) - z y + log1p(exp(-|z|)),  dz = (sigmoid(z) - y) * gscale,  rowid[j] = b.
+    A lookup whose inv is outside [0, cap) or whose field is outside [0, F) contributes nothing. ``w0``: fp32
+    tensor whose first element is the bias (None: 0). ``blocks`` > 0 forces the GPU grid size. One fused gfx950
+    launch on the GPU (no atomics, the same bits for every grid size); the CPU path is the fp32 PyTorch
+    reference of the same rule, samples padded to the batch's max nnz."""
+    F, k, B, n = int(F), int(k), rowptr.numel() - 1, inv.numel()
+    if _gpu(rows):
+        dev = rows.device
+        z, dz, loss = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+        rowid = torch.empty(n, dtype=torch.int32, device=dev)
+        ffmk().ffm_forward(rowptr, inv, vals, fields, labels, rows, F, k, w0, float(gscale), z, dz, loss, rowid,
+                           int(blocks))
+        return z, dz, loss, rowid
+    _ffm_check(F, k, rows.shape[1])
+    cap, FK = rows.shape[0], F * k
+    pos, inside, ok, r, f, x, rowid = _ffm_padded(rowptr, inv, vals, fields, cap, F)
+    Mx = pos.shape[1]
+    slots = rows[:, :FK].float().reshape(cap * F, k)
+    # (the linear term summed as fm_forward's reference sums it: in lookup order, by index_add_)
+    z = torch.zeros(B, dtype=torch.float32).index_add_(
+        0, torch.arange(B)[:, None].expand(B, Mx)[ok], rows[:, FK].float()[r[ok]] * x[ok])
+    upper = torch.triu(torch.ones(Mx, Mx, dtype=torch.bool), diagonal=1)
+    for lo, hi in _ffm_chunks(B, Mx, k):
+        rr, ff, xx = r[lo:hi], f[lo:hi], x[lo:hi]
+        A = slots[rr[:, :, None] * F + ff[:, None, :]]  # A[b, i, j] = v_{inv[i], fields[j]}
+        P = (A * A.transpose(1, 2)).sum(-1) * (xx[:, :, None] * xx[:, None, :])
+        z[lo:hi] += (P * upper).sum((1, 2))
+    if w0 is not None:
+        z = z + w0.reshape(-1)[0].float()
+    y = (labels > 0.5).float()
+    loss = z.clamp(min=0) - z * y + torch.log1p(torch.exp(-z.abs()))
+    dz = (torch.sigmoid(z) - y) * torch.tensor(float(gscale), dtype=torch.float32)
+    return z, dz, loss, rowid.to(torch.int32)
+
+
+def ffm_backward(inv, rowid, rowptr, vals, fields, dz, rows, F, k, grad_rows, csr=None, blocks=0):
+    """Gradient of every unique pulled row of ffm_forward's batch (csrc/kernels/ffm.h): with c_m = dz[rowid[m]] *
+    vals[m] over the lookups m of row u (inv[m] == u), grad_rows[u, g k + c] = sum_m c_m sum_j rows[inv[j],
+    fields[m] k + c] vals[j] over the other lookups j of m's sample with fields[j] == g, grad_rows[u, F k] =
+    sum_m c_m, the three pad columns are 0; rows without lookups are left untouched. Self is skipped, not
+    subtracted. ``csr`` = (members, memrow): the lookups grouped by unique row (a plan's lookup CSR; built from
+    ``inv`` here when absent on the GPU, ignored on the CPU). On the GPU every such row is written exactly once
+    in a fixed summation order -- no atomics, the same bits on every run and for every grid size (``blocks``) --
+    and everything is recomputed from ``rows``, a member or sample index (``csr``, ``rowid``) out of range is
+    skipped. The CPU reference sums with index_add_ and takes every lookup's sample from ``rowptr``: it reads
+    neither ``rowid`` nor ``csr``."""
+    F, k = int(F), int(k)
+    if _gpu(rows):
+        if csr is None:
+            csr = emb_build_csr(inv, 1, max(rows.shape[0], 1))
+        ffmk().ffm_backward(csr[0], csr[1], rowid, rowptr, inv, vals, fields, dz, rows, F, k, grad_rows, int(blocks))
+        return grad_rows
+    _ffm_check(F, k, rows.shape[1])
+    cap, FK, W = rows.shape[0], F * k, F * k + 4
+    if grad_rows.shape[1] != W or grad_rows.shape[0] < cap:
+        raise RuntimeError(f"ffm_backward: grad_rows {tuple(grad_rows.shape)}, expected [>= {cap}, {W}]")
+    if inv.numel() == 0 or dz.numel() == 0:
+        return grad_rows
+    pos, inside, ok, r, f, x, _ = _ffm_padded(rowptr, inv, vals, fields, cap, F)
+    B, Mx = pos.shape
+    c = dz.float()[:, None] * x  # [B, Mx]: 0 where the lookup does not count
+    slots = rows[:, :FK].float().reshape(cap * F, k)
+    acc = torch.zeros(cap * F, k, dtype=torch.float32)
+    lin = torch.zeros(cap, dtype=torch.float32).index_add_(0, r[ok], c[ok])
+    off = ~torch.eye(Mx, dtype=torch.bool)
+    for lo, hi in _ffm_chunks(B, Mx, k):
+        rr, ff, xx, oo = r[lo:hi], f[lo:hi], x[lo:hi], ok[lo:hi]
+        pair = oo[:, :, None] & oo[:, None, :] & off  # [b, member i, partner j]
+        # member i of row inv[i] receives, in slot fields[j], c_i x_j v_{inv[j], fields[i]}
+        src = (rr[:, None, :] * F + ff[:, :, None]).expand(-1, Mx, Mx)[pair]
+        dst = (rr[:, :, None] * F + ff[:, None, :]).expand(-1, Mx, Mx)[pair]
+        s = (c[lo:hi][:, :, None] * xx[:, None, :]).expand(-1, Mx, Mx)[pair]
+        acc.index_add_(0, dst, slots[src] * s[:, None])
+    touched = torch.zeros(cap, dtype=torch.bool)  # every row of the lookup CSR is written, as on the GPU
+    touched[inv[(inv >= 0) & (inv < cap)]] = True
+    out = torch.zeros(cap, W, dtype=torch.float32)
+    out[:, :FK] = acc.reshape(cap, FK)
+    out[:, FK] = lin
+    grad_rows[:cap][touched] = out[touched]
     return grad_rows
 
 

@@ -12,6 +12,9 @@ num_iters (= --steps), alpha (LR). Extra: --fail_rank/--fail_step fault injectio
 every widedeep flag applies, the final JSON gains fm_term, SSP / ASP need --transport collective.
 --model dcn is widedeep with --cross_layers (default 3, 1..4) Deep & Cross layers over its whole input
 (WideDeepConfig(cross_layers=L)): every widedeep flag applies, the final JSON gains cross_layers, collective only.
+--model ffm is the field-aware FM (models/ffm.py): --ffm_k factors per partner field; the synthetic stream takes
+--fm_fields / --fm_card, an --input file --ffm_fields F [--ffm_field_bounds a,b,...] (a key's field is its key
+range); the final JSON gains ffm_fields and ffm_k, collective only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -37,7 +40,7 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm", "dcn"])
+                                                             "deepfm", "dcn", "ffm"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -135,6 +138,14 @@ def parse(argv=None):
                     help="fm, synthetic data: fields per sample, one active feature each (0: 8 with --small, else 64)")
     ap.add_argument("--fm_card", type=int, default=0,
                     help="fm, synthetic data: ids per field (0: 32 with --small, else 262144)")
+    ap.add_argument("--ffm_k", type=int, default=4,
+                    help="ffm: factors per feature and partner field (k % 4 == 0, 4 <= k <= 16)")
+    ap.add_argument("--ffm_fields", type=int, default=0,
+                    help="ffm with --input: fields F of the file's keys (1 <= F <= 64, F * ffm_k <= 512); the "
+                         "synthetic stream takes --fm_fields")
+    ap.add_argument("--ffm_field_bounds", default="",
+                    help="ffm with --input: F - 1 ascending key boundaries a,b,... over the loaded keys (the "
+                         "file's ids minus one); default: equal key ranges")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -146,8 +157,8 @@ def parse(argv=None):
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     if args.wide_optimizer == "ftrl":
-        if args.model not in ("widedeep", "deepfm", "dcn", "fm"):
-            ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm, dcn and fm, not {args.model}")
+        if args.model not in ("widedeep", "deepfm", "dcn", "fm", "ffm"):
+            ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm, dcn, fm and ffm, not {args.model}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
         if not 0 <= args.ftrl_grad_scale < float("inf"):
@@ -163,8 +174,8 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm"):
-        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm and fm, not "
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm", "ffm"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm and ffm, not "
                  f"{args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
@@ -177,6 +188,32 @@ def parse(argv=None):
             ap.error(f"--model fm keeps float32 rows, not --value_dtype {args.value_dtype}")
         if args.eval_every > 0 and args.input:
             ap.error("--model fm: --eval_every needs the synthetic stream (an --input file has no held-out split)")
+    if args.model == "ffm":
+        fields = args.ffm_fields if args.input else (args.fm_fields or (8 if args.small else 64))
+        if args.ffm_k % 4 or not 4 <= args.ffm_k <= 16:
+            ap.error(f"--model ffm: --ffm_k {args.ffm_k} must be a multiple of 4 in [4, 16]")
+        if args.input and not args.ffm_fields:
+            ap.error("--model ffm with --input needs --ffm_fields (the fields of the file's keys)")
+        if not 1 <= fields <= 64 or fields * args.ffm_k > 512:
+            ap.error(f"--model ffm: {fields} fields with --ffm_k {args.ffm_k}: 1 <= fields <= 64 and fields * ffm_k "
+                     f"<= 512")
+        try:
+            args.ffm_bounds = [int(v) for v in args.ffm_field_bounds.split(",") if v.strip()] or None
+        except ValueError:
+            ap.error(f"--ffm_field_bounds {args.ffm_field_bounds!r}: comma-separated integer keys")
+        if args.ffm_bounds is not None and (not args.input or len(args.ffm_bounds) != fields - 1 or any(
+                b <= a for a, b in zip(args.ffm_bounds, args.ffm_bounds[1:]))):
+            ap.error(f"--ffm_field_bounds: --input only, --ffm_fields - 1 = {fields - 1} ascending keys")
+        if args.transport == "onesided":
+            ap.error("--model ffm needs --transport collective (no ffm on the one-sided transport)")
+        if args.kStorageType != "vector":
+            ap.error("--model ffm needs --kStorageType Vector (no ffm on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model ffm keeps float32 rows, not --value_dtype {args.value_dtype}")
+        if args.eval_every > 0 and args.input:
+            ap.error("--model ffm: --eval_every needs the synthetic stream (an --input file has no held-out split)")
+    elif args.ffm_fields or args.ffm_field_bounds:
+        ap.error(f"--ffm_fields / --ffm_field_bounds: --model ffm only, not {args.model}")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
         args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm", "dcn")
                           and args.consistency in ("ssp", "asp") else "collective")
@@ -220,6 +257,18 @@ def _fm_cfg(args, comm, nd: int, B: int):
                    linear_l1=args.ftrl_l1, linear_l2=args.ftrl_l2, linear_grad_scale=args.ftrl_grad_scale)
     return FMConfig(num_dims=nd, k=args.fm_k, lr=args.alpha, consistency=args.consistency, staleness=args.staleness,
                     seed=args.seed, **lin)
+
+
+def _ffm_cfg(args, comm, nd: int, fields: int):
+    """FFMConfig of --model ffm (--wide_optimizer ftrl: the linear column on FTRL with the --ftrl_* flags)."""
+    from .models.ffm import FFMConfig
+
+    lin = {}
+    if args.wide_optimizer == "ftrl":
+        lin = dict(linear_optimizer="ftrl", linear_alpha=args.ftrl_alpha, linear_beta=args.ftrl_beta,
+                   linear_l1=args.ftrl_l1, linear_l2=args.ftrl_l2, linear_grad_scale=args.ftrl_grad_scale)
+    return FFMConfig(num_dims=nd, num_fields=fields, k=args.ffm_k, field_bounds=args.ffm_bounds, lr=args.alpha,
+                     consistency=args.consistency, staleness=args.staleness, seed=args.seed, **lin)
 
 
 def _load_input(args, comm):
@@ -370,6 +419,32 @@ def build(args, comm):
         # one teacher for every rank (seed), this rank's own sample stream
         return m, {0: m.table, **({1: m.bias} if m.bias is not None else {})}, \
             (lambda: _Skippable(FMSynth(B, fields=fields, card=card, device=dev, seed=args.seed).holdout(seed + 1))), \
+            (lambda b: m.train_step(*b)), B
+    if args.model == "ffm" and args.input:
+        # a libsvm file through the LR loader path; a key's field comes from its key range
+        from .models.ffm import FFM
+
+        shard = args._shard.to(dev)
+        nd = args.num_dims
+        if not nd:  # every rank must size the table alike: max feature id over all shards
+            t = torch.tensor([float(shard.cols.max()) + 1 if shard.cols.numel() else 1.0], device=dev)
+            comm.all_reduce_(t, op=dist.ReduceOp.MAX)
+            nd = int(t.item())
+        B = args.batch or 1024
+        m = FFM(_ffm_cfg(args, comm, nd, args.ffm_fields), comm)
+        return m, {0: m.table, **({1: m.bias} if m.bias is not None else {})}, \
+            (lambda: _Skippable(_Batches(shard, B, seed))), (lambda b: m.train_step(*b)), B
+    if args.model == "ffm":
+        from .data.synthetic import FFMSynth
+        from .models.ffm import FFM
+
+        fields = args.fm_fields or (8 if args.small else 64)
+        card = args.fm_card or (32 if args.small else 262144)
+        B = args.batch or (128 if args.small else 16384)
+        m = FFM(_ffm_cfg(args, comm, fields * card, fields), comm)
+        # one teacher for every rank (seed), this rank's own sample stream
+        return m, {0: m.table, **({1: m.bias} if m.bias is not None else {})}, \
+            (lambda: _Skippable(FFMSynth(B, fields=fields, card=card, device=dev, seed=args.seed).holdout(seed + 1))), \
             (lambda b: m.train_step(*b)), B
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
@@ -592,7 +667,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans", "fm") and args.input:
+    if args.model in ("lr", "kmeans", "fm", "ffm") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -827,7 +902,7 @@ def main(argv=None):
     ftrl_final = {}
     if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
         ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
-    if args.wide_optimizer == "ftrl" and args.model == "fm":  # likewise a collective
+    if args.wide_optimizer == "ftrl" and args.model in ("fm", "ffm"):  # likewise a collective
         ftrl_final = dict(linear_nnz=model.linear_nnz(), wide_optimizer="ftrl")
     elif args.wide_optimizer == "ftrl":  # likewise a collective
         ftrl_final = dict(wide_nnz=model.wide_nnz(), wide_optimizer="ftrl")
@@ -835,6 +910,8 @@ def main(argv=None):
         ftrl_final["fm_term"] = True
     if args.model == "dcn":
         ftrl_final["cross_layers"] = args.cross_layers
+    if args.model == "ffm":
+        ftrl_final.update(ffm_fields=model.cfg.num_fields, ffm_k=model.cfg.k)
     clip_final = {}
     if args.clip_norm:
         cs = tables[0].clip_stats()

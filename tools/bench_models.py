@@ -11,7 +11,7 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         samples/s), kmeans (samples/s), widedeep-ssp (config 3), widedeep (the same driver under BSP; takes
         --wide_optimizer ftrl and reports wide_nnz), deepfm (widedeep with the FM term over its embeddings,
         WideDeepConfig(fm_term=True)), dcn (widedeep with --cross_layers Deep & Cross layers over its input,
-        WideDeepConfig(cross_layers=L)).
+        WideDeepConfig(cross_layers=L)), ffm (the field-aware FM, --ffm_fields x 262144 features, --ffm_k).
 """
 from __future__ import annotations
 
@@ -126,6 +126,31 @@ def build(args, comm):
         return m, (lambda: m.train_step(*data.next())), B, "samples/s", \
             dict(model=f"factorization machine k={args.fm_k}, {fields * card} features, {fields} nnz/row, fp32 rows "
                        f"of {args.fm_k + 4}", seq_len=None, **({"linear_optimizer": "ftrl"} if lin else {}))
+    if args.model == "ffm":
+        from minips_amd.data.synthetic import FFMSynth
+        from minips_amd.models.ffm import FFM, FFMConfig
+
+        B = args.batch or 16384
+        fields, card = args.ffm_fields, 262144  # 26 fields: 6.8M features, 26 nnz/row (Criteo's categorical shape)
+        lin = {}
+        if args.wide_optimizer == "ftrl":
+            lin = dict(linear_optimizer="ftrl", linear_alpha=args.ftrl_alpha, linear_beta=args.ftrl_beta,
+                       linear_l1=args.ftrl_l1, linear_l2=args.ftrl_l2, linear_grad_scale=args.ftrl_grad_scale)
+        m = FFM(FFMConfig(num_dims=fields * card, num_fields=fields, k=args.ffm_k, consistency=args.consistency,
+                          staleness=args.staleness, **lin), comm)
+        # (a rank-1 teacher and a ring of ready batches: the field-aware teacher's logits are a [B, F, F] gather,
+        # data generation that is not the model's step)
+        data = FFMSynth(B, fields=fields, card=card, k_teacher=1, device=dev, seed=0).holdout(1000 + r)
+        ring, at = [data.next() for _ in range(4)], [0]
+
+        def step():
+            at[0] += 1
+            return m.train_step(*ring[at[0] % len(ring)])
+
+        return m, step, B, "samples/s", \
+            dict(model=f"field-aware factorization machine k={args.ffm_k}, {fields} fields, {fields * card} features, "
+                       f"{fields} nnz/row, fp32 rows of {fields * args.ffm_k + 4}", seq_len=None,
+                 **({"linear_optimizer": "ftrl"} if lin else {}))
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -203,7 +228,7 @@ def build(args, comm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
-                                                         "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn"])
+                                                         "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -239,9 +264,11 @@ def main():
     ap.add_argument("--ftrl_grad_scale", type=float, default=0.0, help="widedeep ftrl: 0 = batch size x world")
     ap.add_argument("--fm_k", "--fm-k", dest="fm_k", type=int, default=16, help="fm: factors per feature")
     ap.add_argument("--cross_layers", type=int, default=3, help="dcn: cross layers, 1..4")
+    ap.add_argument("--ffm_k", "--ffm-k", dest="ffm_k", type=int, default=4, help="ffm: factors per partner field")
+    ap.add_argument("--ffm_fields", "--ffm-fields", dest="ffm_fields", type=int, default=26, help="ffm: fields")
     args = ap.parse_args()
-    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "fm"):
-        ap.error("--wide_optimizer ftrl: --model widedeep, deepfm, dcn and fm only")
+    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "fm", "ffm"):
+        ap.error("--wide_optimizer ftrl: --model widedeep, deepfm, dcn, fm and ffm only")
     if args.model == "dcn" and not 1 <= args.cross_layers <= 4:
         ap.error("--model dcn: --cross_layers must be in [1, 4]")
     if args.sparse_optimizer == "ftrl" and (args.model != "lr" or args.value_dtype != "float32"):
@@ -274,7 +301,7 @@ def main():
     el = float(t)
     if args.sparse_optimizer == "ftrl":  # after the timed window: a host read (collective)
         cfg["nnz"] = model.nnz()
-    if args.wide_optimizer == "ftrl" and args.model == "fm":  # likewise
+    if args.wide_optimizer == "ftrl" and args.model in ("fm", "ffm"):  # likewise
         cfg["linear_nnz"] = model.linear_nnz()
     elif args.wide_optimizer == "ftrl":  # likewise
         cfg["wide_nnz"] = model.wide_nnz()

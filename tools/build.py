@@ -23,6 +23,8 @@ Targets
             input: a seventh small torch extension, over k_deepfm.o only)
   dcn_py    csrc/bindings/dcn_py.cpp     -> minips_amd/_dcnk*.so     (the Deep & Cross layers on the Wide & Deep
             input: an eighth small torch extension, over k_dcn.o only)
+  ffm_py    csrc/bindings/ffm_py.cpp     -> minips_amd/_ffmk*.so     (the field-aware factorization-machine forward
+            and backward: a ninth small torch extension, over k_ffm.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -261,6 +263,11 @@ def build_dcn_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "dcn_py", "_dcnk", "k_dcn.o")
 
 
+def build_ffm_py(kobjs: list[str]) -> str:
+    """minips_amd/_ffmk: the field-aware factorization-machine binding over k_ffm.o alone."""
+    return _build_small_ext(kobjs, "ffm_py", "_ffmk", "k_ffm.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -288,7 +295,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 def main(argv: list[str]) -> int:
     targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
-                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py"}
+                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py", "ffm_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -304,7 +311,8 @@ def main(argv: list[str]) -> int:
     if "apps" in targets:
         for o in build_apps(objs):
             print("built", o)
-    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py"}:
+    if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py",
+                  "ffm_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -323,6 +331,8 @@ def main(argv: list[str]) -> int:
             print("built", build_deepfm_py(kobjs))
         if targets & {"kernels", "dcn_py"}:
             print("built", build_dcn_py(kobjs))
+        if targets & {"kernels", "ffm_py"}:
+            print("built", build_ffm_py(kobjs))
     return 0
 
 
