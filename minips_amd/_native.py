@@ -22,6 +22,8 @@
   ``ops.wd_cross_backward`` / ``ops.wd_cross_fold``): an eighth small torch extension, same rule.
 * ``_ffmk``     -- the field-aware factorization-machine forward and backward over a CSR batch of pulled rows
   (``ops.ffm_forward`` / ``ops.ffm_backward``): a ninth small torch extension, same rule.
+* ``_gbdtk``    -- the fixed-point histogram GBDT kernels (``ops.gbdt_bin`` / ``gbdt_grad`` / ``gbdt_hist`` /
+  ``gbdt_split`` / ``gbdt_leaf`` / ``gbdt_advance`` / ``gbdt_predict``): a tenth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -102,6 +104,11 @@ def ffmk():
     return _load("_ffmk", "gfx950 HIP field-aware factorization-machine kernels")
 
 
+def gbdtk():
+    """Return the HIP histogram GBDT kernel module or raise a loud error."""
+    return _load("_gbdtk", "gfx950 HIP histogram GBDT kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -141,6 +148,10 @@ def dcnk_available() -> bool:
 
 def ffmk_available() -> bool:
     return _available(ffmk)
+
+
+def gbdtk_available() -> bool:
+    return _available(gbdtk)
 
 
 def native_dir() -> str:

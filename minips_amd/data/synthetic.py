@@ -265,3 +265,37 @@ class FFMSynth(FMSynth):
         a = self.v[cols2d]  # [B, F, F, k]: a[b, f, g] = V[c_f, g]
         pair = (a * a.transpose(1, 2)).sum(-1)
         return self.w[cols2d].sum(1) + (pair * self.upper).sum((1, 2))
+
+
+class GBDTSynth:
+    """Dense batches for the gradient-boosted trees (models/gbdt.py): X [batch, features] ~ U(-1, 1) with
+    features >= 5, and a teacher no linear model can follow,
+    z* = 3 sign(x0) sign(x1) + 2 [x2 > 0.3] x3 - 1.5 [|x4| < 0.4], labels ~ Bernoulli(sigmoid(z*)); the other
+    features are noise. next() returns (X fp32, labels fp32)."""
+
+    def __init__(self, batch: int, features: int = 8, device="cpu", seed: int = 0):
+        if features < 5:
+            raise ValueError(f"GBDTSynth: the teacher reads 5 features, got features = {features}")
+        self.batch, self.features = batch, features
+        self.device = torch.device(device)
+        self.gen = torch.Generator(device=self.device)
+        self.gen.manual_seed(seed + 1)
+
+    def holdout(self, seed: int) -> "GBDTSynth":
+        """A held-out stream of the SAME teacher: an independent sample stream drawn from ``seed``."""
+        g = GBDTSynth.__new__(GBDTSynth)
+        g.__dict__.update(self.__dict__)
+        g.gen = torch.Generator(device=self.device)
+        g.gen.manual_seed(seed)
+        return g
+
+    @staticmethod
+    def teacher_logits(X: torch.Tensor) -> torch.Tensor:
+        return 3.0 * torch.sign(X[:, 0]) * torch.sign(X[:, 1]) + 2.0 * (X[:, 2] > 0.3).float() * X[:, 3] \
+            - 1.5 * (X[:, 4].abs() < 0.4).float()
+
+    def next(self):
+        X = torch.rand(self.batch, self.features, generator=self.gen, device=self.device) * 2.0 - 1.0
+        p = torch.sigmoid(self.teacher_logits(X))
+        y = (torch.rand(self.batch, generator=self.gen, device=self.device) < p).float()
+        return X, y

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, kernels, optk, wdftrlk
+from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1216,6 +1216,222 @@ def ffm_backward(inv, rowid, rowptr, vals, fields, dz, rows, F, k, grad_rows, cs
     out[:, FK] = lin
     grad_rows[:cap][touched] = out[touched]
     return grad_rows
+
+
+# ----------------------------------------------------------------------------- histogram GBDT in fixed point
+GBDT_MAX_BINS, GBDT_MAX_DEPTH, GBDT_MAX_F = 256, 8, 4096  # csrc/kernels/gbdt.h (the binding exports them too)
+GBDT_SCALE = 1 << 20
+_GBDT_ROWS = 1 << 16  # samples per pass of the CPU references
+
+
+def _gbdt_hist_dims(hist):
+    if hist.dim() != 4 or hist.shape[3] != 3 or hist.dtype != torch.int64:
+        raise RuntimeError(f"gbdt: hist must be int64 [nodes, F, NB, 3], got {hist.dtype} {tuple(hist.shape)}")
+    nodes, F, NB = hist.shape[:3]
+    if not (1 <= nodes <= 1 << (GBDT_MAX_DEPTH - 1) and nodes & (nodes - 1) == 0 and 1 <= F <= GBDT_MAX_F
+            and 2 <= NB <= GBDT_MAX_BINS):
+        raise RuntimeError(f"gbdt: hist {tuple(hist.shape)}: nodes a power of two <= 128, 1 <= F <= {GBDT_MAX_F}, "
+                           f"2 <= NB <= {GBDT_MAX_BINS}")
+    return nodes, F, NB
+
+
+def gbdt_bin(X, cuts, out=None, blocks=0):
+    """bins uint8 [N, ldb] of fp32 features X [N, F] against cuts fp32 [F, NB - 1] (ascending per feature, padded
+    with +inf; the rule: csrc/kernels/gbdt.h): bin(x, f) = #{j : x > cuts[f, j]}, comparisons only (NaN -> 0).
+    ``out``: a uint8 [N, >= F] matrix to fill (columns >= F untouched); None allocates zeros with ldb =
+    align16(F). ``blocks`` > 0 forces the GPU grid size."""
+    N, F = X.shape[0], cuts.shape[0]
+    if out is None:
+        out = torch.zeros(N, (F + 15) & ~15, dtype=torch.uint8, device=X.device)
+    if _gpu(X):
+        gbdtk().gbdt_bin(X, cuts, out, int(blocks))
+        return out
+    NB = cuts.shape[1] + 1
+    if X.dim() != 2 or X.shape[1] != F or not (1 <= F <= GBDT_MAX_F and 2 <= NB <= GBDT_MAX_BINS) or \
+            out.shape[0] != N or out.shape[1] < F:
+        raise RuntimeError(f"gbdt_bin: X {tuple(X.shape)}, cuts {tuple(cuts.shape)}, bins {tuple(out.shape)}")
+    step = max(1, (1 << 24) // (F * NB))
+    for lo in range(0, N, step):
+        x = X[lo:lo + step].float()
+        out[lo:lo + step, :F] = (x[:, :, None] > cuts[None]).sum(-1).to(torch.uint8)
+    return out
+
+
+def gbdt_grad(z, labels, gh, loss_acc, blocks=0):
+    """Fixed-point gradients of the logistic loss (csrc/kernels/gbdt.h): gh int32 [N, 2] = (llrint((p - y) 2^20),
+    llrint(max(p (1 - p), 2^-20) 2^20)) with p = sigmoid(clamp(z, -30, 30)) in fp32, y = labels > 0.5; adds
+    sum llrint(loss 2^24) to the int64 ``loss_acc`` [1] (loss: the evalmetrics formula)."""
+    if _gpu(z):
+        gbdtk().gbdt_grad(z, labels, gh, loss_acc, int(blocks))
+        return gh
+    N = z.numel()
+    if gh.shape != (N, 2) or gh.dtype != torch.int32 or labels.numel() != N or loss_acc.dtype != torch.int64:
+        raise RuntimeError(f"gbdt_grad: z [{N}], labels [{labels.numel()}], gh {gh.dtype} {tuple(gh.shape)}")
+    S = float(GBDT_SCALE)
+    y = (labels > 0.5).float()
+    p = 1.0 / (1.0 + torch.exp(-z.float().clamp(-30.0, 30.0)))
+    gh[:, 0] = torch.round((p - y) * S).to(torch.int32)
+    gh[:, 1] = torch.round((p * (1.0 - p)).clamp(min=1.0 / S) * S).to(torch.int32)
+    zl = z.float().clamp(-64.0, 64.0)
+    l = zl.clamp(min=0.0) - zl * y + torch.log1p(torch.exp(-zl.abs()))
+    loss_acc += torch.round(l * 16777216.0).to(torch.int64).sum()
+    return gh
+
+
+def gbdt_hist(bins, node, gh, hist, path=0, blocks=0):
+    """ADDS the level's gradient histograms into ``hist`` int64 [nodes, F, NB, 3] (sum qg, sum qh, count): sample
+    i with 0 <= node[i] < nodes contributes once per feature f at bins[i, f]; a node id out of range or a bin >=
+    NB contributes nothing. Integer sums only: the same bits for every ``path`` (0 auto, 1 LDS accumulators, 2
+    global atomics) and ``blocks`` (> 0 forces the workgroups along the samples) and on the CPU."""
+    if _gpu(hist):
+        gbdtk().gbdt_hist(bins, node, gh, hist, int(path), int(blocks))
+        return hist
+    if path not in (0, 1, 2):
+        raise RuntimeError(f"gbdt_hist: path {path}: 0 auto, 1 LDS, 2 global")
+    return _gbdt_hist_ref(bins, node, gh, hist)
+
+
+def _gbdt_hist_ref(bins, node, gh, hist):
+    """The PyTorch composition of gbdt_hist (index_add_ into int64), on the tensors' device."""
+    nodes, F, NB = _gbdt_hist_dims(hist)
+    N = node.numel()
+    if bins.dim() != 2 or bins.shape[0] != N or bins.shape[1] < F or gh.shape != (N, 2):
+        raise RuntimeError(f"gbdt_hist: bins {tuple(bins.shape)}, node [{N}], gh {tuple(gh.shape)}")
+    flat = hist.view(-1, 3)
+    fs = torch.arange(F, dtype=torch.int64, device=hist.device)
+    for lo in range(0, N, _GBDT_ROWS):
+        nd = node[lo:lo + _GBDT_ROWS].long()
+        b = bins[lo:lo + _GBDT_ROWS, :F].long()
+        g = gh[lo:lo + _GBDT_ROWS].long()
+        ok = ((nd >= 0) & (nd < nodes))[:, None] & (b < NB)
+        idx = ((nd[:, None] * F + fs[None, :]) * NB + b)[ok]
+        v = torch.cat([g, torch.ones(g.shape[0], 1, dtype=torch.int64, device=g.device)],
+                      1)[:, None, :].expand(-1, F, -1)[ok]
+        flat.index_add_(0, idx, v)
+    return hist
+
+
+def gbdt_split(hist, reg_lambda, min_child_count, min_gain, feat, thr, gain, child):
+    """The best split of every node from ``hist`` alone (csrc/kernels/gbdt.h): candidates (f, t), left = bins <= t;
+    gain = (GL GL / (HL + lambda) + GR GR / (HR + lambda)) - G G / (H + lambda) in fp64, every operation rounded
+    on its own; valid with both counts >= min_child_count and gain > min_gain; largest gain, then lowest f, then
+    lowest t. Writes feat / thr int32 [nodes] (feat -1, thr 0, gain 0: no valid split), gain fp64 [nodes], child
+    int64 [nodes, 2, 3] (left and right sums; no split: feature 0's totals | zeros)."""
+    if _gpu(hist):
+        gbdtk().gbdt_split(hist, float(reg_lambda), int(min_child_count), float(min_gain), feat, thr, gain, child)
+        return feat, thr, gain, child
+    return _gbdt_split_ref(hist, reg_lambda, min_child_count, min_gain, feat, thr, gain, child)
+
+
+def _gbdt_split_ref(hist, reg_lambda, min_child_count, min_gain, feat, thr, gain, child):
+    """The PyTorch composition of gbdt_split (cumsum, the gain in fp64 op by op, the first maximum), on the
+    tensors' device."""
+    nodes, F, NB = _gbdt_hist_dims(hist)
+    if not reg_lambda > 0 or min_child_count < 1 or not min_gain >= 0:
+        raise RuntimeError(f"gbdt_split: reg_lambda {reg_lambda} > 0, min_child_count {min_child_count} >= 1, "
+                           f"min_gain {min_gain} >= 0")
+    sc = 1.0 / GBDT_SCALE
+    cum = hist.cumsum(2)
+    tot, L = cum[:, :, -1, :], cum[:, :, :NB - 1, :]
+    R = tot[:, :, None, :] - L
+    GL, HL, GR, HR = L[..., 0].double() * sc, L[..., 1].double() * sc, R[..., 0].double() * sc, R[..., 1].double() * sc
+    G, H = tot[..., 0].double() * sc, tot[..., 1].double() * sc
+    g = (GL * GL / (HL + reg_lambda) + GR * GR / (HR + reg_lambda)) - (G * G / (H + reg_lambda))[:, :, None]
+    ok = (L[..., 2] >= min_child_count) & (R[..., 2] >= min_child_count) & (g > min_gain)
+    g = torch.where(ok, g, torch.full_like(g, -math.inf)).reshape(nodes, F * (NB - 1))
+    mx = g.max(1).values
+    ids = torch.arange(F * (NB - 1), dtype=torch.int64, device=hist.device)
+    first = torch.where(g == mx[:, None], ids[None, :], torch.full_like(ids, F * NB)[None, :]).min(1).values
+    some = mx > -math.inf
+    first = torch.where(some, first, torch.zeros_like(first))
+    f, t = first // (NB - 1), first % (NB - 1)
+    n = torch.arange(nodes, device=hist.device)
+    left = torch.where(some[:, None], L[n, f, t], tot[:, 0])
+    right = torch.where(some[:, None], tot[n, f] - left, torch.zeros_like(left))
+    feat.copy_(torch.where(some, f, torch.full_like(f, -1)))
+    thr.copy_(torch.where(some, t, torch.zeros_like(t)))
+    gain.copy_(torch.where(some, mx, torch.zeros_like(mx)))
+    child[:, 0], child[:, 1] = left, right
+    return feat, thr, gain, child
+
+
+def gbdt_leaf(child, reg_lambda, lr, leaf):
+    """leaf fp32 [2 nodes] from a level's ``child`` [nodes, 2, 3]: leaf[2 n + s] = (float)(-(Gs 2^-20) / (Hs 2^-20 +
+    lambda) * lr) in fp64 with every operation rounded on its own; a child with count 0 gets +0.0."""
+    if _gpu(child):
+        gbdtk().gbdt_leaf(child, float(reg_lambda), float(lr), leaf)
+        return leaf
+    if child.dim() != 3 or child.shape[1:] != (2, 3) or leaf.numel() != 2 * child.shape[0] or not reg_lambda > 0 \
+            or not lr > 0:
+        raise RuntimeError(f"gbdt_leaf: child {tuple(child.shape)}, leaf {tuple(leaf.shape)}, reg_lambda "
+                           f"{reg_lambda}, lr {lr}")
+    c = child.reshape(-1, 3)
+    sc = 1.0 / GBDT_SCALE
+    v = (-(c[:, 0].double() * sc)) / (c[:, 1].double() * sc + reg_lambda) * lr
+    leaf.copy_(torch.where(c[:, 2] == 0, torch.zeros_like(v), v).float())
+    return leaf
+
+
+def gbdt_advance(bins, node, feat, thr, F, leaf=None, z=None, blocks=0):
+    """node[i] <- 2 node[i] + (feat[node[i]] >= 0 and bins[i, feat] > thr), in place (a node id outside [0, nodes)
+    or a feat >= F gives -1). With ``leaf`` [2 nodes] and ``z`` [N] (the last level) also z[i] += leaf[node'[i]]."""
+    if (leaf is None) != (z is None):
+        raise RuntimeError("gbdt_advance: leaf and z come together")
+    if _gpu(node):
+        gbdtk().gbdt_advance(bins, node, feat, thr, int(F), leaf, z, int(blocks))
+        return node
+    return _gbdt_advance_ref(bins, node, feat, thr, F, leaf, z)
+
+
+def _gbdt_advance_ref(bins, node, feat, thr, F, leaf=None, z=None):
+    """The PyTorch composition of gbdt_advance, on the tensors' device."""
+    N, nodes = node.numel(), feat.numel()
+    if bins.dim() != 2 or bins.shape[0] != N or bins.shape[1] < F or thr.numel() != nodes:
+        raise RuntimeError(f"gbdt_advance: bins {tuple(bins.shape)}, node [{N}], feat [{nodes}], thr [{thr.numel()}]")
+    if N == 0:
+        return node
+    nd = node.long()
+    ok = (nd >= 0) & (nd < nodes)
+    ndc = nd.clamp(0, nodes - 1)
+    f = feat.long()[ndc]
+    ok &= f < F
+    b = bins[torch.arange(N, device=node.device), f.clamp(0, F - 1)].long()
+    right = (f >= 0) & (b > thr.long()[ndc])
+    out = torch.where(ok, 2 * nd + right.long(), torch.full_like(nd, -1))
+    node.copy_(out)
+    if leaf is not None:
+        m = out >= 0
+        z[m] = z[m] + leaf[out[m]]
+    return node
+
+
+def gbdt_predict(bins, feat, thr, leaf, F, depth, base, z, leaf_index=None, blocks=0):
+    """z[i] = base + sum_t leaf[t, leaf of sample i in tree t], summed in fp32 in tree order, over complete
+    level-major trees feat int32 / thr uint8 [T, 2^depth - 1], leaf fp32 [T, 2^depth]; optionally ``leaf_index``
+    int32 [N, T]."""
+    if _gpu(z):
+        gbdtk().gbdt_predict(bins, feat, thr, leaf, int(F), int(depth), float(base), z, leaf_index, int(blocks))
+        return z
+    N, T, nn = z.numel(), feat.shape[0], (1 << depth) - 1
+    if not 1 <= depth <= GBDT_MAX_DEPTH or feat.shape != (T, nn) or thr.shape != (T, nn) or \
+            leaf.shape != (T, nn + 1) or bins.shape[0] != N or bins.shape[1] < F or \
+            (leaf_index is not None and leaf_index.shape != (N, T)):
+        raise RuntimeError(f"gbdt_predict: depth {depth}, feat {tuple(feat.shape)}, thr {tuple(thr.shape)}, leaf "
+                           f"{tuple(leaf.shape)}, bins {tuple(bins.shape)}, z [{N}]")
+    s = torch.full((N,), float(base), dtype=torch.float32)
+    rows = torch.arange(N)
+    for t in range(T):
+        n = torch.zeros(N, dtype=torch.int64)
+        for d in range(depth):
+            at = (1 << d) - 1 + n
+            f = feat[t].long()[at]
+            b = bins[rows, f.clamp(0, F - 1)].long() if N else n
+            n = 2 * n + ((f >= 0) & (f < F) & (b > thr[t].long()[at])).long()
+        s = s + leaf[t][n]
+        if leaf_index is not None:
+            leaf_index[:, t] = n.to(torch.int32)
+    z.copy_(s)
+    return z
 
 
 # ----------------------------------------------------------------------------- optimizers

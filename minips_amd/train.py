@@ -15,6 +15,10 @@ every widedeep flag applies, the final JSON gains fm_term, SSP / ASP need --tran
 --model ffm is the field-aware FM (models/ffm.py): --ffm_k factors per partner field; the synthetic stream takes
 --fm_fields / --fm_card, an --input file --ffm_fields F [--ffm_field_bounds a,b,...] (a key's field is its key
 range); the final JSON gains ffm_fields and ffm_k, collective only.
+--model gbdt is the fixed-point histogram GBDT (models/gbdt.py): --steps counts boosting rounds over a resident
+shard -- --gbdt_rows synthetic samples per rank (GBDTSynth), or an --input libsvm file densified to
+--gbdt_features columns (an absent feature is 0.0); --gbdt_depth / --gbdt_bins / --gbdt_lr / --gbdt_lambda,
+--gbdt_model_out PATH saves the trees; the final JSON gains gbdt_trees, gbdt_depth and gbdt_bins, collective only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -40,7 +44,7 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm", "dcn", "ffm"])
+                                                             "deepfm", "dcn", "ffm", "gbdt"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -146,6 +150,16 @@ def parse(argv=None):
     ap.add_argument("--ffm_field_bounds", default="",
                     help="ffm with --input: F - 1 ascending key boundaries a,b,... over the loaded keys (the "
                          "file's ids minus one); default: equal key ranges")
+    ap.add_argument("--gbdt_depth", type=int, default=None, help="gbdt: tree depth, 1..8 (default 6)")
+    ap.add_argument("--gbdt_bins", type=int, default=None, help="gbdt: bins per feature, 2..256 (default 64)")
+    ap.add_argument("--gbdt_lr", type=float, default=None, help="gbdt: shrinkage of every tree (default 0.1)")
+    ap.add_argument("--gbdt_lambda", type=float, default=None, help="gbdt: L2 on the leaf values, > 0 (default 1.0)")
+    ap.add_argument("--gbdt_rows", type=int, default=None,
+                    help="gbdt, synthetic data: resident samples per rank (default 4096 with --small, else 1048576)")
+    ap.add_argument("--gbdt_features", type=int, default=None,
+                    help="gbdt: feature columns (synthetic: >= 5, default 8; with --input: required, keys beyond "
+                         "it are dropped)")
+    ap.add_argument("--gbdt_model_out", default="", help="gbdt: rank 0 saves the cuts and the trees here at the end")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -174,9 +188,50 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm", "ffm"):
-        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm and ffm, not "
-                 f"{args.model}")
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm", "ffm", "gbdt"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm, ffm and gbdt, "
+                 f"not {args.model}")
+    gbdt_flags = [f"--{k}" for k in ("gbdt_depth", "gbdt_bins", "gbdt_lr", "gbdt_lambda", "gbdt_rows",
+                                     "gbdt_features") if getattr(args, k) is not None]
+    if args.gbdt_model_out:
+        gbdt_flags.append("--gbdt_model_out")
+    if args.model == "gbdt":
+        args.gbdt_depth = 6 if args.gbdt_depth is None else args.gbdt_depth
+        args.gbdt_bins = 64 if args.gbdt_bins is None else args.gbdt_bins
+        args.gbdt_lr = 0.1 if args.gbdt_lr is None else args.gbdt_lr
+        args.gbdt_lambda = 1.0 if args.gbdt_lambda is None else args.gbdt_lambda
+        if not 1 <= args.gbdt_depth <= 8:
+            ap.error(f"--model gbdt: --gbdt_depth {args.gbdt_depth} must be in [1, 8]")
+        if not 2 <= args.gbdt_bins <= 256:
+            ap.error(f"--model gbdt: --gbdt_bins {args.gbdt_bins} must be in [2, 256]")
+        if not args.gbdt_lr > 0 or not args.gbdt_lambda > 0:
+            ap.error("--model gbdt: --gbdt_lr and --gbdt_lambda must be > 0")
+        if args.input and args.gbdt_features is None:
+            ap.error("--model gbdt with --input needs --gbdt_features (the columns the file is densified to)")
+        if args.input and args.gbdt_rows is not None:
+            ap.error("--model gbdt: --gbdt_rows sizes the synthetic shard, not an --input file")
+        args.gbdt_features = 8 if args.gbdt_features is None else args.gbdt_features
+        if not 1 <= args.gbdt_features <= 4096 or (not args.input and args.gbdt_features < 5):
+            ap.error(f"--model gbdt: --gbdt_features {args.gbdt_features} must be in [1, 4096] (the synthetic "
+                     f"teacher reads 5)")
+        args.gbdt_rows = (4096 if args.small else 1 << 20) if args.gbdt_rows is None else args.gbdt_rows
+        if args.gbdt_rows < 1:
+            ap.error(f"--model gbdt: --gbdt_rows {args.gbdt_rows} must be >= 1")
+        if (1 << (args.gbdt_depth - 1)) * args.gbdt_features * args.gbdt_bins * 24 > 1 << 30:
+            ap.error("--model gbdt: the last level's histogram [2^(depth-1), features, bins, 3] int64 is above 1 GiB")
+        if args.steps > 65536:
+            ap.error(f"--model gbdt: --steps {args.steps} boosting rounds, at most 65536 trees")
+        if args.transport == "onesided":
+            ap.error("--model gbdt needs --transport collective (no gbdt on the one-sided transport)")
+        if args.consistency != "bsp":
+            ap.error("--model gbdt is bulk-synchronous: every level all-reduces its histogram (--consistency bsp)")
+        if args.checkpoint_toggle or args.use_weight_file:
+            ap.error("--model gbdt: no table checkpoints (--gbdt_model_out saves the trees; an elastic restart of a "
+                     "boosting run is out of scope)")
+        if args.eval_every > 0 and args.input:
+            ap.error("--model gbdt: --eval_every needs the synthetic stream (an --input file has no held-out split)")
+    elif gbdt_flags:
+        ap.error(f"{' / '.join(gbdt_flags)}: --model gbdt only, not {args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -296,6 +351,22 @@ def _load_input(args, comm):
         print(f"[rank 0] block assigner: {srv.local_served} local / {srv.remote_served} remote blocks", flush=True)
         srv.stop()
     return data
+
+
+class _Resident:
+    """The data stream of --model gbdt: the shard is resident in the model, a boosting round draws nothing."""
+
+    def __init__(self, synth):
+        self.synth = synth
+
+    def next(self):
+        return None
+
+    def skip(self, k: int):
+        pass
+
+    def holdout(self, seed: int):
+        return self.synth.holdout(seed)
 
 
 SMALL_CARDS = [50, 7, 300, 20, 5, 60, 90, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27,
@@ -446,6 +517,29 @@ def build(args, comm):
         return m, {0: m.table, **({1: m.bias} if m.bias is not None else {})}, \
             (lambda: _Skippable(FFMSynth(B, fields=fields, card=card, device=dev, seed=args.seed).holdout(seed + 1))), \
             (lambda b: m.train_step(*b)), B
+    if args.model == "gbdt":
+        from .data.synthetic import GBDTSynth
+        from .models.gbdt import GBDT, GBDTConfig
+
+        F = args.gbdt_features
+        m = GBDT(GBDTConfig(num_features=F, num_bins=args.gbdt_bins, depth=args.gbdt_depth, lr=args.gbdt_lr,
+                            reg_lambda=args.gbdt_lambda, max_trees=max(args.steps, 1)), comm)
+        synth = None
+        if args.input:  # the libsvm shard densified once: an absent feature is 0.0, keys beyond F are dropped
+            shard = args._shard.to(dev)
+            X = torch.zeros(shard.n, F, dtype=torch.float32, device=dev)
+            row = torch.repeat_interleave(torch.arange(shard.n, device=dev), shard.rowptr[1:] - shard.rowptr[:-1])
+            ok = (shard.cols >= 0) & (shard.cols < F)
+            X.index_put_((row[ok], shard.cols[ok]), shard.vals[ok], accumulate=True)
+            y = shard.labels
+        else:  # one teacher, this rank's own samples
+            synth = GBDTSynth(args.gbdt_rows, features=F, device=dev, seed=args.seed).holdout(seed + 1)
+            X, y = synth.next()
+        m.make_cuts(X)
+        m.attach(X, y)
+        rows = X.shape[0]
+        # boost() returns the loss summed over every rank's samples
+        return m, {}, (lambda: _Resident(synth)), (lambda b: m.boost() / comm.world), max(rows, 1)
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
         # shard stays resident in HBM and batches are consecutive rows, cut on the device
@@ -667,7 +761,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans", "fm", "ffm") and args.input:
+    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -894,12 +988,18 @@ def main(argv=None):
         return float(a.double().sum())
 
     sums = torch.tensor([_param_sum(t) for t in tables.values()], dtype=torch.float64, device=comm.device)
-    comm.all_reduce_(sums)
+    if tables:
+        comm.all_reduce_(sums)
     if comm.device.type == "cuda":
         torch.cuda.synchronize(comm.device)
     if hb:
         hb.stop()
     ftrl_final = {}
+    if args.model == "gbdt":  # every rank holds the same trees: the checksum is the sum of their leaves
+        sums = model.leaf[: model.num_trees].double().sum().reshape(1)
+        ftrl_final.update(gbdt_trees=model.num_trees, gbdt_depth=model.cfg.depth, gbdt_bins=model.cfg.num_bins)
+        if args.gbdt_model_out and comm.rank == 0:
+            model.save(args.gbdt_model_out)
     if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
         ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
     if args.wide_optimizer == "ftrl" and args.model in ("fm", "ffm"):  # likewise a collective

@@ -11,7 +11,9 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         samples/s), kmeans (samples/s), widedeep-ssp (config 3), widedeep (the same driver under BSP; takes
         --wide_optimizer ftrl and reports wide_nnz), deepfm (widedeep with the FM term over its embeddings,
         WideDeepConfig(fm_term=True)), dcn (widedeep with --cross_layers Deep & Cross layers over its input,
-        WideDeepConfig(cross_layers=L)), ffm (the field-aware FM, --ffm_fields x 262144 features, --ffm_k).
+        WideDeepConfig(cross_layers=L)), ffm (the field-aware FM, --ffm_fields x 262144 features, --ffm_k),
+        gbdt (a boosting round of the fixed-point histogram GBDT over --batch resident samples per rank; --gbdt_depth,
+        --gbdt_bins, --gbdt_features; ms_per_step is ms per tree).
 """
 from __future__ import annotations
 
@@ -151,6 +153,22 @@ def build(args, comm):
             dict(model=f"field-aware factorization machine k={args.ffm_k}, {fields} fields, {fields * card} features, "
                        f"{fields} nnz/row, fp32 rows of {fields * args.ffm_k + 4}", seq_len=None,
                  **({"linear_optimizer": "ftrl"} if lin else {}))
+    if args.model == "gbdt":
+        from minips_amd.data.synthetic import GBDTSynth
+        from minips_amd.models.gbdt import GBDT, GBDTConfig
+
+        # a boosting round over a resident shard of --batch samples per rank (default 4M x 32 features, 64 bins,
+        # depth 6); a "step" is one tree: max_trees covers the warm-up and the timed rounds
+        rows = args.batch or 1 << 22
+        m = GBDT(GBDTConfig(num_features=args.gbdt_features, num_bins=args.gbdt_bins, depth=args.gbdt_depth,
+                            max_trees=args.steps + args.warmup + 1), comm)
+        X, y = GBDTSynth(rows, features=args.gbdt_features, device=dev, seed=0).holdout(1000 + r).next()
+        m.make_cuts(X[: 1 << 20])
+        m.attach(X, y)
+        del X
+        return m, m.boost, rows, "samples/s", \
+            dict(model=f"histogram GBDT depth {args.gbdt_depth}, {args.gbdt_bins} bins, {args.gbdt_features} features, "
+                       f"{rows} resident samples per rank, int64 fixed-point histograms", seq_len=None)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -228,7 +246,8 @@ def build(args, comm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
-                                                         "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm"])
+                                                         "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
+                                                         "gbdt"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -266,6 +285,10 @@ def main():
     ap.add_argument("--cross_layers", type=int, default=3, help="dcn: cross layers, 1..4")
     ap.add_argument("--ffm_k", "--ffm-k", dest="ffm_k", type=int, default=4, help="ffm: factors per partner field")
     ap.add_argument("--ffm_fields", "--ffm-fields", dest="ffm_fields", type=int, default=26, help="ffm: fields")
+    ap.add_argument("--gbdt_depth", "--gbdt-depth", dest="gbdt_depth", type=int, default=6, help="gbdt: tree depth")
+    ap.add_argument("--gbdt_bins", "--gbdt-bins", dest="gbdt_bins", type=int, default=64, help="gbdt: bins")
+    ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
+                    help="gbdt: features (the teacher reads 5)")
     args = ap.parse_args()
     if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "fm", "ffm"):
         ap.error("--wide_optimizer ftrl: --model widedeep, deepfm, dcn, fm and ffm only")

@@ -25,6 +25,8 @@ Targets
             input: an eighth small torch extension, over k_dcn.o only)
   ffm_py    csrc/bindings/ffm_py.cpp     -> minips_amd/_ffmk*.so     (the field-aware factorization-machine forward
             and backward: a ninth small torch extension, over k_ffm.o only)
+  gbdt_py   csrc/bindings/gbdt_py.cpp    -> minips_amd/_gbdtk*.so    (the fixed-point histogram GBDT kernels: a
+            tenth small torch extension, over k_gbdt.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -268,6 +270,11 @@ def build_ffm_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "ffm_py", "_ffmk", "k_ffm.o")
 
 
+def build_gbdt_py(kobjs: list[str]) -> str:
+    """minips_amd/_gbdtk: the histogram GBDT binding over k_gbdt.o alone."""
+    return _build_small_ext(kobjs, "gbdt_py", "_gbdtk", "k_gbdt.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -295,7 +302,7 @@ def build_sanitized(kind: str) -> list[str]:
 
 def main(argv: list[str]) -> int:
     targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
-                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py", "ffm_py"}
+                                  "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py", "ffm_py", "gbdt_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -312,7 +319,7 @@ def main(argv: list[str]) -> int:
         for o in build_apps(objs):
             print("built", o)
     if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py",
-                  "ffm_py"}:
+                  "ffm_py", "gbdt_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -333,6 +340,8 @@ def main(argv: list[str]) -> int:
             print("built", build_dcn_py(kobjs))
         if targets & {"kernels", "ffm_py"}:
             print("built", build_ffm_py(kobjs))
+        if targets & {"kernels", "gbdt_py"}:
+            print("built", build_gbdt_py(kobjs))
     return 0
 
 
