@@ -526,6 +526,7 @@ void check_attn(int T, int H, int dmodel, int ldq, int ldo) {
 
 void attn_fwd(const bf16_t* qkv, int ldq, int B, int T, int H, int dmodel, float scale, bf16_t* O, int ldo, float* lse,
               hipStream_t s) {
+  if (B <= 0 || T <= 0) return;
   check_attn(T, H, dmodel, ldq, ldo);
   const int grid = ((T + BROWS - 1) / BROWS) * B * H;  // decoded as (block of T, head) in the kernels
   // 3 waves per SIMD (the register cap of the template argument; 2 = the uncapped allocation, slower)
@@ -535,6 +536,7 @@ void attn_fwd(const bf16_t* qkv, int ldq, int B, int T, int H, int dmodel, float
 
 void attn_bwd(const bf16_t* qkv, int ldq, const bf16_t* O, int ldo, const bf16_t* dO, int lddo, const float* lse,
               float* delta, int B, int T, int H, int dmodel, float scale, bf16_t* dqkv, int lddq, hipStream_t s) {
+  if (B <= 0 || T <= 0) return;
   check_attn(T, H, dmodel, ldq, lddq);
   const int64_t rows = (int64_t)B * T;
   hipLaunchKernelGGL(attn_prep_kernel, (int)((rows * H * 8 + 255) / 256), 256, 0, s, O, ldo, dO, lddo, rows, T, H,

@@ -86,16 +86,24 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __rest
       if (c < C) {
         ld4(x + r * ldx + c, v[k]);
 #pragma unroll
+        for (int q = 0; q < 4; ++q) s += v[k][q];
+      }
+    }
+    const float mu = warp_sum(s) / C;
+    // the variance from the centred row (it is in registers): E[x^2] - mean^2 cancels in fp32 once
+    // |mean| >> std (rstd off by 4e-3 at mean / std = 200)
+#pragma unroll
+    for (int k = 0; k < kLnK; ++k) {
+      const int c = k * 256 + lane * 4;
+      if (c < C) {
+#pragma unroll
         for (int q = 0; q < 4; ++q) {
-          s += v[k][q];
-          ss += v[k][q] * v[k][q];
+          const float dv = v[k][q] - mu;
+          ss += dv * dv;
         }
       }
     }
-    s = warp_sum(s);
-    ss = warp_sum(ss);
-    const float mu = s / C;
-    const float rs = rsqrtf(fmaxf(ss / C - mu * mu, 0.f) + eps);
+    const float rs = rsqrtf(warp_sum(ss) / C + eps);
 #pragma unroll
     for (int k = 0; k < kLnK; ++k) {
       const int c = k * 256 + lane * 4;

@@ -1679,9 +1679,10 @@ def layernorm_fwd(x, C, gamma, beta, eps, y, mean, rstd):
         return y
     xf = x[:, :C].float()
     mu = xf.mean(1)
-    var = (xf * xf).mean(1) - mu * mu
-    rs = torch.rsqrt(var.clamp_min(0) + eps)
-    y[:, :C] = ((xf - mu[:, None]) * rs[:, None] * gamma.float() + beta.float()).to(torch.bfloat16)
+    xc = xf - mu[:, None]
+    # two passes, as the kernel: E[x^2] - mean^2 cancels in fp32 once |mean| >> std
+    rs = torch.rsqrt((xc * xc).mean(1) + eps)
+    y[:, :C] = (xc * rs[:, None] * gamma.float() + beta.float()).to(torch.bfloat16)
     mean.copy_(mu)
     rstd.copy_(rs)
     return y
