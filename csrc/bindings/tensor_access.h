@@ -34,6 +34,7 @@ template <> struct dtype_of<bf16_t> { static constexpr at::ScalarType value = at
 template <> struct dtype_of<int64_t> { static constexpr at::ScalarType value = at::kLong; };
 template <> struct dtype_of<int32_t> { static constexpr at::ScalarType value = at::kInt; };
 template <> struct dtype_of<uint8_t> { static constexpr at::ScalarType value = at::kByte; };
+template <> struct dtype_of<int16_t> { static constexpr at::ScalarType value = at::kShort; };
 
 inline bool present(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
 

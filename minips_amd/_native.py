@@ -24,6 +24,8 @@
   (``ops.ffm_forward`` / ``ops.ffm_backward``): a ninth small torch extension, same rule.
 * ``_gbdtk``    -- the fixed-point histogram GBDT kernels (``ops.gbdt_bin`` / ``gbdt_grad`` / ``gbdt_hist`` /
   ``gbdt_split`` / ``gbdt_leaf`` / ``gbdt_advance`` / ``gbdt_predict``): a tenth small torch extension, same rule.
+* ``_ldak``     -- the fixed-point LDA collapsed Gibbs kernels (``ops.lda_sample`` / ``lda_delta`` /
+  ``lda_loglik``): an eleventh small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -109,6 +111,11 @@ def gbdtk():
     return _load("_gbdtk", "gfx950 HIP histogram GBDT kernels")
 
 
+def ldak():
+    """Return the HIP LDA Gibbs kernel module or raise a loud error."""
+    return _load("_ldak", "gfx950 HIP LDA Gibbs kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -152,6 +159,10 @@ def ffmk_available() -> bool:
 
 def gbdtk_available() -> bool:
     return _available(gbdtk)
+
+
+def ldak_available() -> bool:
+    return _available(ldak)
 
 
 def native_dir() -> str:

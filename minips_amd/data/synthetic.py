@@ -299,3 +299,44 @@ class GBDTSynth:
         p = torch.sigmoid(self.teacher_logits(X))
         y = (torch.rand(self.batch, generator=self.gen, device=self.device) < p).float()
         return X, y
+
+
+class LDASynth:
+    """A corpus with planted topics for Latent Dirichlet Allocation (models/lda.py): topic k owns the word block
+    [k * (vocab // topics), (k + 1) * (vocab // topics)) with word weights from Dirichlet(1) (disjoint blocks),
+    every document mixes the topics with weights from Dirichlet(0.2) and draws ``doc_len`` tokens. corpus()
+    returns (rowptr int64 [docs + 1], words int64 [docs * doc_len], planted): ``planted`` is the planted model's
+    own per-token log likelihood of the corpus, mean log(sum_k theta[d, k] phi[k, w]) in nats. Generated on the
+    host from ``seed`` alone; ``phi`` [topics, vocab] and ``theta`` [docs, topics] stay on the object."""
+
+    def __init__(self, topics: int = 4, vocab: int = 64, docs: int = 256, doc_len: int = 48, seed: int = 0,
+                 mix: float = 0.2):
+        if topics < 1 or vocab < topics or docs < 1 or doc_len < 1:
+            raise ValueError(f"LDASynth: topics {topics}, vocab {vocab}, docs {docs}, doc_len {doc_len}: every topic "
+                             f"needs a word block of its own")
+        self.topics, self.vocab, self.docs, self.doc_len, self.block = topics, vocab, docs, doc_len, vocab // topics
+        gen = torch.Generator()
+        gen.manual_seed(seed + 1)
+        # Dirichlet(c) = normalised Gamma(c, 1); Gamma(1) is -log U, Gamma(c) by torch's sampler
+        e = -torch.log1p(-torch.rand(topics, self.block, generator=gen, dtype=torch.float64))
+        self.phi = torch.zeros(topics, vocab, dtype=torch.float64)
+        for k in range(topics):
+            self.phi[k, k * self.block:(k + 1) * self.block] = e[k] / e[k].sum()
+        g = torch._standard_gamma(torch.full((docs, topics), float(mix), dtype=torch.float64), generator=gen)
+        g = g.clamp(min=1e-300)
+        self.theta = g / g.sum(1, keepdim=True)
+        self.zs = torch.multinomial(self.theta, doc_len, replacement=True, generator=gen)          # [docs, doc_len]
+        self.words = torch.multinomial(self.phi[self.zs.reshape(-1)], 1, generator=gen).reshape(-1)
+        self.rowptr = torch.arange(docs + 1, dtype=torch.int64) * doc_len
+
+    def planted_loglik(self) -> float:
+        doc = torch.arange(self.docs).repeat_interleave(self.doc_len)
+        p = (self.theta[doc] * self.phi[:, self.words].t()).sum(1)
+        return float(torch.log(p).mean())
+
+    def corpus(self):
+        return self.rowptr, self.words, self.planted_loglik()
+
+    def block_of(self, words: torch.Tensor) -> torch.Tensor:
+        """The planted topic whose block holds each word (words past the last block: the last topic)."""
+        return (words // self.block).clamp(max=self.topics - 1)

@@ -2,10 +2,10 @@
 
 Every op has ONE device implementation: GPU tensors go to the hand-written gfx950 HIP
 kernels in ``minips_amd._kernels`` (the evaluation, gradient-clipping, FTRL, Adagrad + FTRL and factorization-machine
-ops: in the small extensions ``_evalk`` / ``_optk`` / ``_ftrlk`` / ``_wdftrlk`` / ``_fmk``) and raise if that
-extension is missing -- there is no silent eager fallback on a GPU. CPU tensors run a plain PyTorch reference of
-the same math; that path exists for the CPU/gloo plumbing configuration (BASELINE config 1) and as the fp32 oracle
-the GPU numerics tests compare against.
+ops: in the small extensions ``_evalk`` / ``_optk`` / ``_ftrlk`` / ``_wdftrlk`` / ``_fmk``; the LDA ops: in
+``_ldak``) and raise if that extension is missing -- there is no silent eager fallback on a GPU. CPU tensors run a
+plain PyTorch reference of the same math; that path exists for the CPU/gloo plumbing configuration (BASELINE
+config 1) and as the fp32 oracle the GPU numerics tests compare against.
 """
 from __future__ import annotations
 
@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, optk, wdftrlk
+from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, ldak, optk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1432,6 +1432,223 @@ def gbdt_predict(bins, feat, thr, leaf, F, depth, base, z, leaf_index=None, bloc
             leaf_index[:, t] = n.to(torch.int32)
     z.copy_(s)
     return z
+
+
+# ----------------------------------------------------------------------------- LDA collapsed Gibbs in fixed point
+LDA_MIN_K, LDA_MAX_K, LDA_MAX_DOC_LEN = 2, 1024, 4096  # csrc/kernels/lda.h (the binding exports them too)
+LDA_MAX_PRIOR = 64.0
+LDA_LOGLIK_SCALE = float(1 << 24)
+_LDA_GOLD = 0x9E3779B97F4A7C15
+_LDA_M64 = (1 << 64) - 1
+_LDA_M32 = (1 << 32) - 1
+
+
+def _lda_s64(x: int) -> int:
+    """The int64 that holds the bits of the uint64 x."""
+    x &= _LDA_M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def lda_mix_int(x: int) -> int:
+    """mix of csrc/kernels/lda.h on a Python integer (mod 2^64)."""
+    x &= _LDA_M64
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _LDA_M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _LDA_M64
+    x ^= x >> 31
+    return x
+
+
+def _lda_lsr(x: torch.Tensor, s: int) -> torch.Tensor:
+    return (x >> s) & ((1 << (64 - s)) - 1)  # the logical shift of the uint64 held in an int64
+
+
+def _lda_mix(x: torch.Tensor) -> torch.Tensor:
+    """mix on int64 tensors holding uint64 bits (torch's int64 products wrap mod 2^64)."""
+    x = x ^ _lda_lsr(x, 30)
+    x = x * _lda_s64(0xBF58476D1CE4E5B9)
+    x = x ^ _lda_lsr(x, 27)
+    x = x * _lda_s64(0x94D049BB133111EB)
+    return x ^ _lda_lsr(x, 31)
+
+
+def mulhi_u64(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The high 64 bits of the 128-bit product of two uint64 held in int64 tensors, from 32-bit limbs."""
+    al, ah, bl, bh = a & _LDA_M32, _lda_lsr(a, 32), b & _LDA_M32, _lda_lsr(b, 32)
+    ll, lh, hl, hh = al * bl, al * bh, ah * bl, ah * bh
+    mid = _lda_lsr(ll, 32) + (lh & _LDA_M32) + (hl & _LDA_M32)
+    return hh + _lda_lsr(lh, 32) + _lda_lsr(hl, 32) + _lda_lsr(mid, 32)
+
+
+def _lda_check(op, K, alpha, beta, Vbeta, rows, blocks=0):
+    if not LDA_MIN_K <= K <= LDA_MAX_K:
+        raise RuntimeError(f"{op}: nk says K = {K}, expected {LDA_MIN_K} <= K <= {LDA_MAX_K}")
+    if not (0 < alpha <= LDA_MAX_PRIOR and 0 < beta <= LDA_MAX_PRIOR):
+        raise RuntimeError(f"{op}: alpha is {alpha} and beta {beta}, expected both in (0, 64]")
+    if not 0 < Vbeta < float("inf"):
+        raise RuntimeError(f"{op}: Vbeta is {Vbeta}, expected a positive finite V * beta")
+    if rows.dim() != 2 or rows.shape[1] < K or rows.dtype != torch.float32:
+        raise RuntimeError(f"{op}: rows must be fp32 [cap, >= {K}], got {rows.dtype} {tuple(rows.shape)}")
+    if not 0 <= blocks <= 65535:
+        raise RuntimeError(f"{op}: blocks is {blocks}, expected 0 <= blocks <= 65535")
+
+
+def _lda_tokens(rowptr, n):
+    """The tokens the documents cover: (lo [B], lens [B], doc [m], pos [m], t [m]) with t = lo[doc] + pos."""
+    lo = rowptr[:-1].clamp(0, n)
+    hi = torch.maximum(rowptr[1:].clamp(0, n), lo)
+    lens = hi - lo
+    B = lens.numel()
+    doc = torch.repeat_interleave(torch.arange(B, dtype=torch.int64), lens)
+    start = torch.cumsum(lens, 0) - lens
+    pos = torch.arange(doc.numel(), dtype=torch.int64) - start[doc]
+    return lo, lens, doc, pos, lo[doc] + pos
+
+
+def lda_sample(rowptr, gid, inv, z_old, rows, nk, alpha, beta, Vbeta, seed, it, z_new=None, dk=None, blocks=0):
+    """One clock of delayed-update collapsed Gibbs sampling for LDA against the snapshot (rows, nk) (the rule:
+    csrc/kernels/lda.h). Document d holds the tokens [rowptr[d], rowptr[d+1]) and has the global id gid[d]; token t
+    reads rows[inv[t]] (fp32 counts [cap, >= K]); nk int64 [K]; z_old int16 [n], or None at the initialisation
+    (it == 0). Returns (z_new int16 [n], dk int64 [K]); ``dk`` is ADDED to: -1 at the old and +1 at the new topic
+    of every token whose topic changed (+1 only at the initialisation). A token whose inv lies outside [0, cap)
+    keeps its topic and contributes nothing. The same bits on the GPU (one wave per document; ``blocks`` > 0 forces
+    the grid) and in this PyTorch reference, which is vectorised across documents and loops over positions."""
+    B, n, K = rowptr.numel() - 1, inv.numel(), nk.numel()
+    alpha, beta, Vbeta, seed, it = float(alpha), float(beta), float(Vbeta), int(seed), int(it)
+    if z_new is None:
+        z_new = torch.empty(n, dtype=torch.int16, device=rows.device)
+    if dk is None:
+        dk = torch.zeros(K, dtype=torch.int64, device=rows.device)
+    if _gpu(rows):
+        ldak().lda_sample(rowptr, gid, inv, z_old, rows, nk, alpha, beta, Vbeta, _lda_s64(seed), it, z_new, dk,
+                          int(blocks))
+        return z_new, dk
+    _lda_check("lda_sample", K, alpha, beta, Vbeta, rows, blocks)
+    if it < 0 or (z_old is None) != (it == 0):
+        raise RuntimeError(f"lda_sample: it is {it}: 0 is the initialisation and takes no z_old, a sweep needs one")
+    if gid.numel() != B or z_new.numel() != n or dk.numel() != K or (z_old is not None and z_old.numel() != n):
+        raise RuntimeError(f"lda_sample: gid [{gid.numel()}] for {B} documents, z_new [{z_new.numel()}] for {n} "
+                           f"tokens, dk [{dk.numel()}] for K = {K}")
+    cap = rows.shape[0]
+    lo, lens, doc, pos, t = _lda_tokens(rowptr, n)
+    base = _lda_s64(lda_mix_int(seed + it * _LDA_GOLD))
+    one = torch.ones(1, dtype=torch.int64)
+    if z_old is None:
+        r = _lda_mix(base ^ (gid[doc] * 4096 + pos))
+        kn = mulhi_u64(r, torch.full_like(r, K))
+        live = (inv[t] >= 0) & (inv[t] < cap)
+        z_new[t] = torch.where(live, kn, torch.full_like(kn, -1)).to(torch.int16)
+        dk.index_add_(0, kn[live], one.expand(int(live.sum())))
+        return z_new, dk
+    z = z_old.long()
+    live_t = (inv >= 0) & (inv < cap) & (z >= 0) & (z < K)
+    z_new[t] = z_old[t]
+    lt = live_t[t]
+    ndk = torch.zeros(B, K, dtype=torch.int64)
+    ndk.view(-1).index_add_(0, (doc * K + z[t])[lt], one.expand(int(lt.sum())))
+    cinv0 = 1.0 / (nk.clamp(min=0).double() + Vbeta)
+    for j in range(int(lens.max()) if B else 0):
+        act = torch.nonzero(lens > j).squeeze(1)
+        tj = lo[act] + j
+        lv = live_t[tj]
+        act, tj = act[lv], tj[lv]
+        a = act.numel()
+        if a == 0:
+            continue
+        A = torch.arange(a)
+        ko, uu = z[tj], inv[tj]
+        nd = ndk[act]
+        nd[A, ko] -= 1
+        av = nd.double() + alpha
+        bv = rows[uu, :K].double()
+        bv[A, ko] -= 1.0
+        bv = bv.clamp(min=0.0) + beta
+        cv = cinv0.expand(a, K).clone()
+        cv[A, ko] = 1.0 / ((nk[ko] - 1).clamp(min=0).double() + Vbeta)
+        x = (av * bv) * cv
+        wt = (x * 1099511627776.0).to(torch.int64) + 1
+        cs = torch.cumsum(wt, 1)
+        r = _lda_mix(base ^ (gid[act] * 4096 + j))
+        target = mulhi_u64(r, cs[:, -1])
+        kn = (cs <= target[:, None]).sum(1).clamp(max=K - 1)
+        nd[A, kn] += 1
+        ndk[act] = nd
+        z_new[tj] = kn.to(torch.int16)
+        ch = kn != ko
+        c = int(ch.sum())
+        dk.index_add_(0, ko[ch], -one.expand(c))
+        dk.index_add_(0, kn[ch], one.expand(c))
+    return z_new, dk
+
+
+def lda_delta(inv, z_old, z_new, K, delta, csr=None, blocks=0):
+    """The count deltas of every unique pulled row of lda_sample's batch (csrc/kernels/lda.h): over the member
+    tokens m of row u (inv[m] == u), delta[u, k] = #{z_new[m] == k} - #{z_old[m] == k} for k < K and 0 for the pad
+    columns of delta fp32 [cap, align4(K)]; z_old None: +1 only (the initialisation). The whole row is written
+    (explicit zeros included); rows without members are left untouched. ``csr`` = (members, memrow): a plan's
+    lookup CSR (built from ``inv`` here when absent on the GPU, ignored on the CPU). On the GPU every such row is
+    written exactly once from an integer LDS histogram -- no global atomics, the same bits for every grid size
+    (``blocks``)."""
+    K = int(K)
+    W = (K + 3) & ~3
+    if _gpu(delta):
+        if csr is None:  # (not the model's path: a plan carries its CSR) rows outside [0, cap) go to a row past the
+            cap = delta.shape[0]  # end, which the kernel ignores: emb_build_csr trusts its rows
+            ok = (inv >= 0) & (inv < cap)
+            csr = emb_build_csr(torch.where(ok, inv, torch.full_like(inv, cap)), 1, cap + 1)
+        ldak().lda_delta(csr[0], csr[1], z_old, z_new, K, delta, int(blocks))
+        return delta
+    n, cap = inv.numel(), delta.shape[0]
+    if not LDA_MIN_K <= K <= LDA_MAX_K or delta.dim() != 2 or delta.shape[1] != W or z_new.numel() != n or \
+            (z_old is not None and z_old.numel() != n):
+        raise RuntimeError(f"lda_delta: K {K}, delta {tuple(delta.shape)} (expected [cap, {W}]), z_new "
+                           f"[{z_new.numel()}] for {n} tokens")
+    if n == 0 or cap == 0:
+        return delta
+    ok = (inv >= 0) & (inv < cap)
+    acc = torch.zeros(cap * W, dtype=torch.int64)
+    for zz, sign in ((z_new, 1), (z_old, -1)):
+        if zz is None:
+            continue
+        zz = zz.long()
+        m = ok & (zz >= 0) & (zz < K)
+        acc.index_add_(0, inv[m] * W + zz[m], torch.full((1,), sign, dtype=torch.int64).expand(int(m.sum())))
+    touched = torch.zeros(cap, dtype=torch.bool)
+    touched[inv[ok]] = True
+    delta[touched] = acc.view(cap, W)[touched].float()
+    return delta
+
+
+def lda_loglik(rowptr, inv, z, rows, nk, alpha, beta, Vbeta, acc, blocks=0):
+    """ADDS the batch's fixed-point log likelihood into acc int64 [2] (csrc/kernels/lda.h): per live token, in
+    fp64, l = log(sum_k ((ndk[k] + alpha) / (L + K alpha)) * ((rows[inv][k] + beta) / (nk[k] + Vbeta))) with the
+    document's own counts ndk and length L; acc[0] += sum llrint(-l 2^24), acc[1] += tokens. The GPU and this
+    reference may differ by one unit per token (the order of the fp64 sum, ``log``)."""
+    B, n, K = rowptr.numel() - 1, inv.numel(), nk.numel()
+    alpha, beta, Vbeta = float(alpha), float(beta), float(Vbeta)
+    if _gpu(rows):
+        ldak().lda_loglik(rowptr, inv, z, rows, nk, alpha, beta, Vbeta, acc, int(blocks))
+        return acc
+    _lda_check("lda_loglik", K, alpha, beta, Vbeta, rows, blocks)
+    if z.numel() != n or acc.numel() != 2 or acc.dtype != torch.int64:
+        raise RuntimeError(f"lda_loglik: z [{z.numel()}] for {n} tokens, acc {acc.dtype} [{acc.numel()}]")
+    cap = rows.shape[0]
+    _, _, doc, _, t = _lda_tokens(rowptr, n)
+    zl = z.long()
+    live = ((inv >= 0) & (inv < cap) & (zl >= 0) & (zl < K))[t]
+    doc, t = doc[live], t[live]
+    ndk = torch.zeros(B, K, dtype=torch.int64)
+    ndk.view(-1).index_add_(0, doc * K + zl[t], torch.ones(1, dtype=torch.int64).expand(t.numel()))
+    theta = (ndk.double() + alpha) / (ndk.sum(1).double() + K * alpha)[:, None]
+    den = nk.double() + Vbeta
+    step = max(1, (1 << 22) // K)
+    for s in range(0, t.numel(), step):
+        phi = (rows[inv[t[s:s + step]], :K].double() + beta) / den
+        p = (theta[doc[s:s + step]] * phi).sum(1)
+        acc[0] += torch.round(-torch.log(p) * LDA_LOGLIK_SCALE).to(torch.int64).sum()
+    acc[1] += t.numel()
+    return acc
 
 
 # ----------------------------------------------------------------------------- optimizers

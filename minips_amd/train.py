@@ -19,6 +19,11 @@ range); the final JSON gains ffm_fields and ffm_k, collective only.
 shard -- --gbdt_rows synthetic samples per rank (GBDTSynth), or an --input libsvm file densified to
 --gbdt_features columns (an absent feature is 0.0); --gbdt_depth / --gbdt_bins / --gbdt_lr / --gbdt_lambda,
 --gbdt_model_out PATH saves the trees; the final JSON gains gbdt_trees, gbdt_depth and gbdt_bins, collective only.
+--model lda is Latent Dirichlet Allocation by fixed-point collapsed Gibbs sampling (models/lda.py): --steps counts
+sweeps over a resident corpus -- --lda_docs synthetic documents of --lda_doc_len tokens over all ranks (LDASynth),
+or an --input libsvm file whose lines are documents (`label word:count ...`, the label is ignored);
+--lda_topics / --lda_alpha / --lda_beta / --lda_vocab, --batch documents per clock; the reported loss is the
+negative per-token log likelihood; the final JSON gains lda_topics, lda_tokens and lda_loglik, collective BSP only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -44,7 +49,7 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm", "dcn", "ffm", "gbdt"])
+                                                             "deepfm", "dcn", "ffm", "gbdt", "lda"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -160,6 +165,16 @@ def parse(argv=None):
                     help="gbdt: feature columns (synthetic: >= 5, default 8; with --input: required, keys beyond "
                          "it are dropped)")
     ap.add_argument("--gbdt_model_out", default="", help="gbdt: rank 0 saves the cuts and the trees here at the end")
+    ap.add_argument("--lda_topics", type=int, default=None, help="lda: topics K, 2..1024 (default 16)")
+    ap.add_argument("--lda_alpha", type=float, default=None, help="lda: document-topic prior, (0, 64] (default 0.1)")
+    ap.add_argument("--lda_beta", type=float, default=None, help="lda: topic-word prior, (0, 64] (default 0.01)")
+    ap.add_argument("--lda_vocab", type=int, default=None,
+                    help="lda: vocabulary size (synthetic default: 256 with --small, else 65536; with --input: the "
+                         "largest word of all shards + 1)")
+    ap.add_argument("--lda_docs", type=int, default=None,
+                    help="lda, synthetic data: documents over all ranks (default 256 with --small, else 65536)")
+    ap.add_argument("--lda_doc_len", type=int, default=None,
+                    help="lda, synthetic data: tokens per document, 1..4096 (default 48 with --small, else 128)")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -232,6 +247,47 @@ def parse(argv=None):
             ap.error("--model gbdt: --eval_every needs the synthetic stream (an --input file has no held-out split)")
     elif gbdt_flags:
         ap.error(f"{' / '.join(gbdt_flags)}: --model gbdt only, not {args.model}")
+    lda_flags = [f"--{k}" for k in ("lda_topics", "lda_alpha", "lda_beta", "lda_vocab", "lda_docs", "lda_doc_len")
+                 if getattr(args, k) is not None]
+    if args.model == "lda":
+        args.lda_topics = 16 if args.lda_topics is None else args.lda_topics
+        args.lda_alpha = 0.1 if args.lda_alpha is None else args.lda_alpha
+        args.lda_beta = 0.01 if args.lda_beta is None else args.lda_beta
+        if not 2 <= args.lda_topics <= 1024:
+            ap.error(f"--model lda: --lda_topics {args.lda_topics} must be in [2, 1024]")
+        if not 0 < args.lda_alpha <= 64 or not 0 < args.lda_beta <= 64:
+            ap.error("--model lda: --lda_alpha and --lda_beta must be in (0, 64]")
+        if args.input and (args.lda_docs is not None or args.lda_doc_len is not None):
+            ap.error("--model lda: --lda_docs / --lda_doc_len size the synthetic corpus, not an --input file")
+        if not args.input:
+            args.lda_vocab = (256 if args.small else 65536) if args.lda_vocab is None else args.lda_vocab
+            args.lda_docs = (256 if args.small else 65536) if args.lda_docs is None else args.lda_docs
+            args.lda_doc_len = (48 if args.small else 128) if args.lda_doc_len is None else args.lda_doc_len
+            if args.lda_docs < 1 or not 1 <= args.lda_doc_len <= 4096:
+                ap.error("--model lda: --lda_docs must be >= 1 and --lda_doc_len in [1, 4096]")
+            if args.lda_vocab < args.lda_topics:
+                ap.error(f"--model lda: --lda_vocab {args.lda_vocab} is below --lda_topics {args.lda_topics} (every "
+                         f"planted topic owns a word block)")
+        if args.lda_vocab is not None and not 1 <= args.lda_vocab < 1 << 31:
+            ap.error(f"--model lda: --lda_vocab {args.lda_vocab} must be in [1, 2^31)")
+        if args.batch < 0:
+            ap.error(f"--model lda: --batch {args.batch} documents per clock must be >= 1 (0: 4096)")
+        if args.transport == "onesided":
+            ap.error("--model lda needs --transport collective (no lda on the one-sided transport)")
+        if args.consistency != "bsp":
+            ap.error("--model lda is bulk-synchronous: every clock all-reduces the topic totals (--consistency bsp; "
+                     "no SSP or ASP)")
+        if args.kStorageType != "vector":
+            ap.error("--model lda needs --kStorageType Vector (no lda on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model lda keeps float32 count rows, not --value_dtype {args.value_dtype}")
+        if args.eval_every > 0:
+            ap.error("--model lda: no --eval_every (held-out fold-in perplexity is out of scope; the loss is the "
+                     "training log likelihood)")
+        if args.checkpoint_toggle or args.use_weight_file:
+            ap.error("--model lda: no table checkpoints (they do not hold the topic of every token)")
+    elif lda_flags:
+        ap.error(f"{' / '.join(lda_flags)}: --model lda only, not {args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -540,6 +596,45 @@ def build(args, comm):
         rows = X.shape[0]
         # boost() returns the loss summed over every rank's samples
         return m, {}, (lambda: _Resident(synth)), (lambda b: m.boost() / comm.world), max(rows, 1)
+    if args.model == "lda":
+        from .models.lda import LDA, LDAConfig
+
+        if args.input:  # every line a document of word:count pairs (the label is ignored); this rank's lines
+            shard = args._shard
+            rp_f, words = shard.rowptr.long().cpu(), shard.cols.long().cpu()
+            cnt = shard.vals.cpu().round().clamp(min=0).long()
+            doc = torch.repeat_interleave(torch.arange(shard.n), rp_f[1:] - rp_f[:-1])
+            words, doc = torch.repeat_interleave(words, cnt), torch.repeat_interleave(doc, cnt)
+            rp = torch.zeros(shard.n + 1, dtype=torch.int64)
+            rp[1:] = torch.cumsum(torch.bincount(doc, minlength=shard.n), 0)
+            t = torch.zeros(comm.world + 1, dtype=torch.int64, device=dev)
+            t[comm.rank] = shard.n
+            comm.all_reduce_(t)  # the documents of the ranks before this one: the global ids
+            base = int(t[: comm.rank].sum())
+            vmax = torch.tensor([int(words.max()) + 1 if words.numel() else 1], dtype=torch.int64, device=dev)
+            comm.all_reduce_(vmax, op=dist.ReduceOp.MAX)
+            V = args.lda_vocab if args.lda_vocab is not None else int(vmax)
+        else:  # one corpus for every rank (seed), this rank's even slice of its documents
+            from .data.synthetic import LDASynth
+            from .ps.tables import even_bounds
+
+            synth = LDASynth(args.lda_topics, args.lda_vocab, args.lda_docs, args.lda_doc_len, seed=args.seed)
+            b = even_bounds(args.lda_docs, comm.world)
+            base, hi = b[comm.rank], b[comm.rank + 1]
+            rp = synth.rowptr[base:hi + 1] - synth.rowptr[base]
+            words = synth.words[int(synth.rowptr[base]):int(synth.rowptr[hi])]
+            V = args.lda_vocab
+        m = LDA(LDAConfig(num_topics=args.lda_topics, vocab=V, alpha=args.lda_alpha, beta=args.lda_beta,
+                          batch_docs=args.batch or 4096, seed=args.seed), comm)
+        m.attach(rp, words, base)
+        m.init()
+
+        def lda_step(_):  # a sweep; the loss (collective, read on the host) at the driver's report intervals only
+            m.sweep()
+            report = m.it % 10 == 0 or m.it == args.steps
+            return torch.tensor([-m.loglik() if report else 0.0], device=dev)
+
+        return m, {}, (lambda: _Resident(None)), lda_step, 1
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
         # shard stays resident in HBM and batches are consecutive rows, cut on the device
@@ -761,7 +856,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt") and args.input:
+    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -1000,6 +1095,9 @@ def main(argv=None):
         ftrl_final.update(gbdt_trees=model.num_trees, gbdt_depth=model.cfg.depth, gbdt_bins=model.cfg.num_bins)
         if args.gbdt_model_out and comm.rank == 0:
             model.save(args.gbdt_model_out)
+    if args.model == "lda":  # the topic totals are replicated: their sum is the corpus's token count
+        sums = model.nk.double().sum().reshape(1)
+        ftrl_final.update(lda_topics=model.K, lda_tokens=int(model.nk.sum()), lda_loglik=round(model.loglik(), 6))
     if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
         ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
     if args.wide_optimizer == "ftrl" and args.model in ("fm", "ffm"):  # likewise a collective

@@ -13,7 +13,8 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         WideDeepConfig(fm_term=True)), dcn (widedeep with --cross_layers Deep & Cross layers over its input,
         WideDeepConfig(cross_layers=L)), ffm (the field-aware FM, --ffm_fields x 262144 features, --ffm_k),
         gbdt (a boosting round of the fixed-point histogram GBDT over --batch resident samples per rank; --gbdt_depth,
-        --gbdt_bins, --gbdt_features; ms_per_step is ms per tree).
+        --gbdt_bins, --gbdt_features; ms_per_step is ms per tree), lda (a sweep of the fixed-point collapsed Gibbs
+        sampler over --batch resident tokens per rank; --lda_topics; ms_per_step is ms per sweep).
 """
 from __future__ import annotations
 
@@ -169,6 +170,25 @@ def build(args, comm):
         return m, m.boost, rows, "samples/s", \
             dict(model=f"histogram GBDT depth {args.gbdt_depth}, {args.gbdt_bins} bins, {args.gbdt_features} features, "
                        f"{rows} resident samples per rank, int64 fixed-point histograms", seq_len=None)
+    if args.model == "lda":
+        from minips_amd.models.lda import LDA, LDAConfig
+        from tools.bench_lda import make_corpus
+
+        # a sweep over a resident corpus of --batch tokens per rank (default 4M, documents of 128 tokens, a power
+        # law over 65536 words), clocks of 8192 documents; a "step" is one sweep
+        tokens = args.batch or 1 << 22
+        rowptr, words = make_corpus(tokens, 128, 1 << 16, dev, seed=r)
+        m = LDA(LDAConfig(num_topics=args.lda_topics, vocab=1 << 16, batch_docs=8192, seed=0), comm)
+        m.attach(rowptr, words, r * (rowptr.numel() - 1))
+        m.init()
+
+        def sweep():
+            m.sweep()
+            return m.nk[:1].float()
+
+        return m, sweep, words.numel(), "tokens/s", \
+            dict(model=f"LDA collapsed Gibbs, {args.lda_topics} topics, 65536 words, {words.numel()} resident tokens "
+                       f"per rank, clocks of 8192 documents, int64 fixed-point weights", seq_len=None)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -247,7 +267,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
                                                          "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
-                                                         "gbdt"])
+                                                         "gbdt", "lda"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -287,6 +307,7 @@ def main():
     ap.add_argument("--ffm_fields", "--ffm-fields", dest="ffm_fields", type=int, default=26, help="ffm: fields")
     ap.add_argument("--gbdt_depth", "--gbdt-depth", dest="gbdt_depth", type=int, default=6, help="gbdt: tree depth")
     ap.add_argument("--gbdt_bins", "--gbdt-bins", dest="gbdt_bins", type=int, default=64, help="gbdt: bins")
+    ap.add_argument("--lda_topics", "--lda-topics", dest="lda_topics", type=int, default=256, help="lda: topics")
     ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
                     help="gbdt: features (the teacher reads 5)")
     args = ap.parse_args()
