@@ -73,4 +73,13 @@ inline int grid_for(int64_t work, int block, int cap = 2048) {
   return (int)g;
 }
 
+// what a launcher asks before it picks a float4 kernel
+inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+inline int pow2ceil(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
 }  // namespace minips_k

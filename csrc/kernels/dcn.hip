@@ -506,8 +506,6 @@ inline int resident_blocks(const void* f) {
   return cus * per;
 }
 
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 void check_shape(const char* op, int64_t ldx, int64_t B, int d, int L, int blocks) {
   if (d < 1 || d > kDcnMaxD || d > ldx)
     throw std::runtime_error(std::string(op) + ": d outside [1, " + std::to_string(kDcnMaxD) + "] or above ldx");

@@ -141,14 +141,6 @@ __global__ __launch_bounds__(kBlock) void wd_fm_backward_kernel(const bf16_t* __
   }
 }
 
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-inline int pow2ceil(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 void check_shape(const char* op, int64_t ldx, int64_t B, int F, int D, int blocks) {
   if (!dfm_shape_ok(F, D, ldx)) throw std::runtime_error(std::string(op) + ": 1 <= D <= 64, F >= 1 and F * D <= ldx");
   if (blocks < 0 || blocks > kDfmMaxBlocks) throw std::runtime_error(std::string(op) + ": blocks outside [0, 65535]");

@@ -38,16 +38,13 @@
 //             shuffles and add those whose field is their slot. By the member count M of the row:
 //             M <= kFfmGroupMax                 one lane group walks the members in order
 //             kFfmGroupMax < M <= kFfmWaveMax   a whole wave: members strided over its groups, fixed-order fold
-//             M > kFfmWaveMax                   workgroups: every kFfmChunk members of the row are summed by one
-//                                               256-thread block (waves folded through LDS) into a partial, and
-//                                               the block that holds the row's first member adds the partials
-//                                               in chunk order (a second launch)
+//             M > kFfmWaveMax                   workgroups, by the chunk rule of member_rows.h: a 256-thread block
+//                                               (waves folded through LDS) per kFfmChunk members
 //             (a member costs nnz_b gathers and a walk over them, not one gather as in the FM: the limits are
 //             far below fm.h's -- with 512 | 256 a Zipf(1.05) batch spent 2.2 ms in rows that one wave walked
 //             alone (profiles/ffm/kernels.txt). A wave takes consecutive tiles of rows, so memrow is searched once
-//             per wave and a row
-//             starts where the row before it ended; a chunk decides by two reads whether it can hold a heavy
-//             row at all. `part` holds 2 W floats per chunk: n W / 4 bytes.)
+//             per wave and a row starts where the row before it ended. `part` holds 2 W floats per chunk:
+//             n W / 4 bytes.)
 // No float atomics anywhere. Every output is a function of the inputs alone: the same bits on every run and for
 // every grid size.
 #pragma once

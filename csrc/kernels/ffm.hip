@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "ffm.h"
+#include "member_rows.h"
 
 namespace minips_k {
 
@@ -14,27 +15,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRedW = kFfmMaxFK + 8;  // a gradient row in LDS (W <= 516)
-
-template <int E>
-__device__ __forceinline__ void load_e(const float* p, float (&a)[E]) {
-  if constexpr (E == 4) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    a[0] = v.x, a[1] = v.y, a[2] = v.z, a[3] = v.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) a[e] = p[e];
-  }
-}
-
-template <int E>
-__device__ __forceinline__ void store_e(float* p, const float (&a)[E]) {
-  if constexpr (E == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(a[0], a[1], a[2], a[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) p[e] = a[e];
-  }
-}
 
 // One wave per sample; lane l takes the pairs l, l + 64, ... of the round-robin enumeration (ffm.h) and the
 // lookups l, l + 64, ... of the linear term.
@@ -98,42 +78,13 @@ __global__ __launch_bounds__(kBlock) void ffm_forward_kernel(
     }
     if (lane == 0) {
       const float zz = (w0v + lin) + acc;
-      const bool y = labels[b] > 0.5f;
-      const float ex = expf(-fabsf(zz));  // in (0, 1]
-      const float big = 1.f / (1.f + ex), small = ex / (1.f + ex);
-      // sigmoid(z) - y without cancellation: sigmoid = big for z >= 0, small below
-      const float sg = zz >= 0.f ? big : small, one_m = zz >= 0.f ? small : big;
+      float dzb, lossb;
+      logistic_head(zz, labels[b] > 0.5f, gscale, &dzb, &lossb);
       z[b] = zz;
-      dz[b] = (y ? -one_m : sg) * gscale;
-      loss[b] = fmaxf(zz, 0.f) - (y ? zz : 0.f) + log1pf(ex);
+      dz[b] = dzb;
+      loss[b] = lossb;
     }
   }
-}
-
-__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ a, int lo, int hi, int key) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// first index in (lo, n) whose value is >= key, given a[lo] < key: doubling steps from lo, then a binary search
-// inside the last step
-__device__ __forceinline__ int gallop_i32(const int32_t* __restrict__ a, int lo, int n, int key) {
-  int step = 1;
-  while (lo + step < n && a[lo + step] < key) {
-    lo += step;
-    step <<= 1;
-  }
-  return lower_bound_i32(a, lo + 1, lo + step < n ? lo + step : n, key);
-}
-
-// first index in [lo, n) whose value is >= key
-__device__ __forceinline__ int first_ge_i32(const int32_t* __restrict__ a, int lo, int n, int key) {
-  if (lo >= n || a[lo] >= key) return lo < n ? lo : n;
-  return gallop_i32(a, lo, n, key);
 }
 
 struct BwdArgs {
@@ -255,11 +206,6 @@ __device__ __forceinline__ void store_row(float* dst, int W, const Lane<E, L, C>
   }
 }
 
-__device__ __forceinline__ int ffm_unique(const BwdArgs& a) {
-  const int64_t U = (int64_t)a.memrow[a.n - 1] + 1;
-  return (int)(U < 0 ? 0 : (U > a.cap ? a.cap : U));
-}
-
 // Rows of up to kFfmWaveMax members: a tile of G consecutive unique rows per wave and iteration, one lane group
 // per row; the rows of a tile that have more than kFfmGroupMax members are then walked by the whole wave.
 template <int E, int L, int C>
@@ -270,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void ffm_backward_kernel(BwdArgs a) {
   const Lane<E, L, C> ln(lane, a.F, a.k);
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int U = ffm_unique(a);
+  const int U = member_unique(a.memrow, a.n, a.cap);
   const int64_t ntiles = ((int64_t)U + G - 1) / G;
   // consecutive tiles per wave: one binary search of memrow per wave, every later row starts by a gallop from
   // where the tile before it ended (`carry`)
@@ -312,25 +258,7 @@ __global__ __launch_bounds__(kBlock) void ffm_backward_kernel(BwdArgs a) {
   }
 }
 
-// A row of more than kFfmWaveMax >= 2 kFfmChunk members is the first or the last row of every chunk it
-// touches. (first row | last row if another) of chunk p; false: no such candidate.
-__device__ __forceinline__ bool ffm_heavy_row(const BwdArgs& a, int64_t p, int s, int& r, int& lo, int& hi) {
-  const int64_t c_lo = p * kFfmChunk, c_hi = (c_lo + kFfmChunk) < a.n ? (c_lo + kFfmChunk) : a.n;
-  const int ra = a.memrow[c_lo], rb = a.memrow[c_hi - 1];
-  if (s == 1 && rb == ra) return false;
-  r = s ? rb : ra;
-  if ((uint64_t)(int64_t)r >= (uint64_t)a.cap) return false;
-  // more than 2 kFfmChunk members in a row that touches this chunk: the row also holds the member half a chunk
-  // before the chunk or the one half a chunk after it (two reads that spare most chunks the two searches)
-  constexpr int H = kFfmChunk / 2;
-  const int64_t after = c_hi - 1 + H;
-  if (!((c_lo >= H && a.memrow[c_lo - H] == r) || (after < a.n && a.memrow[after] == r))) return false;
-  lo = lower_bound_i32(a.memrow, 0, a.n, r);
-  hi = lower_bound_i32(a.memrow, lo, a.n, r + 1);
-  return hi - lo > kFfmWaveMax;
-}
-
-// block p sums the members of chunk p that belong to a heavy row into part[(2 p + s) * W ...]
+// block p sums the members of chunk p that belong to a heavy row into part[(2 p + s) * W ...] (member_rows.h)
 template <int E, int L, int C>
 __global__ __launch_bounds__(kBlock) void ffm_backward_heavy_kernel(BwdArgs a) {
   constexpr int G = 64 / L, NG = G * (kBlock / 64);
@@ -342,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void ffm_backward_heavy_kernel(BwdArgs a) {
   const int64_t c_lo = p * kFfmChunk, c_hi = (c_lo + kFfmChunk) < a.n ? (c_lo + kFfmChunk) : a.n;
   for (int s = 0; s < 2; ++s) {
     int r, lo, hi;
-    if (!ffm_heavy_row(a, p, s, r, lo, hi)) continue;  // block-uniform
+    if (!member_heavy_row<kFfmChunk, kFfmWaveMax>(a.memrow, a.n, a.cap, p, s, r, lo, hi)) continue;  // block-uniform
     const int m0 = lo > c_lo ? lo : (int)c_lo, m1 = hi < c_hi ? hi : (int)c_hi;
     float acc[C][E];
     zero_acc<E, C>(acc);
@@ -368,26 +296,6 @@ __global__ __launch_bounds__(kBlock) void ffm_backward_heavy_kernel(BwdArgs a) {
     }
   }
 }
-
-// the block whose chunk holds a heavy row's first member adds that row's partials in chunk order
-__global__ __launch_bounds__(kBlock) void ffm_backward_heavy_fold_kernel(BwdArgs a) {
-  const int W = a.F * a.k + 4;
-  const int64_t p = blockIdx.x;
-  const int64_t c_lo = p * kFfmChunk;
-  for (int s = 0; s < 2; ++s) {
-    int r, lo, hi;
-    if (!ffm_heavy_row(a, p, s, r, lo, hi)) continue;
-    if (lo < c_lo) continue;  // the row began in an earlier chunk
-    const int64_t q1 = (hi - 1) / kFfmChunk;
-    for (int col = threadIdx.x; col < W; col += kBlock) {
-      float t = a.part[(2 * p + s) * W + col];
-      for (int64_t qc = p + 1; qc <= q1; ++qc) t += a.part[(2 * qc) * W + col];
-      a.grad[(int64_t)r * W + col] = t;
-    }
-  }
-}
-
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 void check_shape(const char* op, int F, int k, int64_t ld, int64_t cap, int64_t B, int64_t n, int blocks) {
   if (!ffm_shape_ok(F, k))
@@ -429,9 +337,10 @@ struct BwdLaunch {
     const int grid = blocks > 0 ? blocks : grid_for(urows * L, kBlock, 8192);
     hipLaunchKernelGGL((ffm_backward_kernel<E, L, C>), grid, kBlock, 0, s, a);
     if (n > kFfmWaveMax) {
-      const int chunks = (int)((n + kFfmChunk - 1) / kFfmChunk);
+      const int chunks = member_chunks(n, kFfmChunk);
       hipLaunchKernelGGL((ffm_backward_heavy_kernel<E, L, C>), chunks, kBlock, 0, s, a);
-      hipLaunchKernelGGL(ffm_backward_heavy_fold_kernel, chunks, kBlock, 0, s, a);
+      hipLaunchKernelGGL((member_heavy_fold_kernel<float, float, kFfmChunk, kFfmWaveMax>), chunks, kBlock, 0, s,
+                         a.memrow, a.n, a.cap, a.F * a.k + 4, a.part, a.grad);
     }
   }
 };
@@ -456,14 +365,13 @@ void ffm_forward(const int64_t* rowptr, const int64_t* inv, const float* vals, c
 }
 
 int64_t ffm_backward_part_floats(int64_t n, int W) {
-  return n > kFfmWaveMax ? 2 * ((n + kFfmChunk - 1) / kFfmChunk) * W : 0;
+  return member_part_elems(n, W, kFfmChunk, kFfmWaveMax);
 }
 
 void ffm_backward(const int32_t* members, const int32_t* memrow, const int32_t* rowid, const int64_t* rowptr,
                   const int64_t* inv, const float* vals, const int32_t* fields, const float* dz, const float* rows,
                   int64_t ld, int64_t cap, int F, int k, int64_t B, int64_t n, float* grad_rows, float* part,
                   int blocks, hipStream_t s) {
-  static_assert(kFfmWaveMax >= 2 * kFfmChunk, "a heavy row must be first or last in every chunk it touches");
   static_assert(kFfmMaxFK + 4 <= kRedW, "a gradient row must fit the LDS fold");
   check_shape("ffm_backward", F, k, ld, cap, B, n, blocks);
   if (n <= 0 || B <= 0 || cap <= 0) return;

@@ -29,10 +29,8 @@
 //             next row starts):
 //             M <= kFmGroupMax (32)            one lane group walks the members in order
 //             kFmGroupMax < M <= kFmWaveMax    a whole wave: members strided over its groups, fixed-order fold
-//             M > kFmWaveMax (2048)            workgroups: every kFmChunk (1024) members of the row are summed
-//                                              by one 256-thread block (waves folded through LDS) into a
-//                                              partial, and the block that holds the row's first member adds
-//                                              the partials in chunk order (a second launch)
+//             M > kFmWaveMax (2048)            workgroups, by the chunk rule of member_rows.h: a 256-thread block
+//                                              (waves folded through LDS) per kFmChunk (1024) members
 // No atomics anywhere; the forward needs no LDS. Every output is a function of the inputs alone: the same
 // bits on every run and for every grid size.
 #pragma once

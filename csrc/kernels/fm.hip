@@ -7,33 +7,13 @@
 
 #include "common.h"
 #include "fm.h"
+#include "member_rows.h"
 
 namespace minips_k {
 
 namespace {
 
 constexpr int kBlock = 256;
-
-template <int E>
-__device__ __forceinline__ void load_e(const float* p, float (&a)[E]) {
-  if constexpr (E == 4) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    a[0] = v.x, a[1] = v.y, a[2] = v.z, a[3] = v.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) a[e] = p[e];
-  }
-}
-
-template <int E>
-__device__ __forceinline__ void store_e(float* p, const float (&a)[E]) {
-  if constexpr (E == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(a[0], a[1], a[2], a[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < E; ++e) p[e] = a[e];
-  }
-}
 
 // One wave per sample. Lane group g (L lanes, lane l owns columns [E l, E l + E)) takes the lookups g, g + G,
 // ... of the sample; the lane that owns column k carries the linear term in its first element.
@@ -110,36 +90,13 @@ __global__ __launch_bounds__(kBlock) void fm_forward_kernel(const int64_t* __res
     }
     if (lane == 0) {
       const float zz = (w0v + lin) + 0.5f * (ss - qq);
-      const bool y = labels[b] > 0.5f;
-      const float ex = expf(-fabsf(zz));            // in (0, 1]
-      const float big = 1.f / (1.f + ex), small = ex / (1.f + ex);
-      // sigmoid(z) - y without cancellation: sigmoid = big for z >= 0, small below
-      const float sg = zz >= 0.f ? big : small, one_m = zz >= 0.f ? small : big;
+      float dzb, lossb;
+      logistic_head(zz, labels[b] > 0.5f, gscale, &dzb, &lossb);
       z[b] = zz;
-      dz[b] = (y ? -one_m : sg) * gscale;
-      loss[b] = fmaxf(zz, 0.f) - (y ? zz : 0.f) + log1pf(ex);
+      dz[b] = dzb;
+      loss[b] = lossb;
     }
   }
-}
-
-__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ a, int lo, int hi, int key) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// first index in (lo, n) whose value is >= key, given a[lo] < key: doubling steps from lo, then a binary search
-// inside the last step (a short segment costs two or three reads, not log2 n)
-__device__ __forceinline__ int gallop_i32(const int32_t* __restrict__ a, int lo, int n, int key) {
-  int step = 1;
-  while (lo + step < n && a[lo + step] < key) {
-    lo += step;
-    step <<= 1;
-  }
-  return lower_bound_i32(a, lo + 1, lo + step < n ? lo + step : n, key);
 }
 
 struct BwdArgs {
@@ -183,11 +140,6 @@ __device__ __forceinline__ void fm_row_values(const BwdArgs& a, int u, int c0, b
   if (fac) load_e<E>(a.rows + (int64_t)u * a.ld + c0, v);
 }
 
-__device__ __forceinline__ int fm_unique(const BwdArgs& a) {
-  const int64_t U = (int64_t)a.memrow[a.n - 1] + 1;
-  return (int)(U < 0 ? 0 : (U > a.cap ? a.cap : U));
-}
-
 // Rows of up to kFmWaveMax members: a tile of G consecutive unique rows per wave and iteration, one lane group
 // per row; the rows of a tile that have more than kFmGroupMax members are then walked by the whole wave.
 template <int E, int L>
@@ -198,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void fm_backward_kernel(BwdArgs a) {
   const bool fac = c0 < a.k, isl = c0 == a.k, wr = c0 < W;
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int U = fm_unique(a);
+  const int U = member_unique(a.memrow, a.n, a.cap);
   const int64_t ntiles = ((int64_t)U + G - 1) / G;
   for (int64_t tile = wave; tile < ntiles; tile += nwaves) {
     const int64_t u64 = tile * G + g;
@@ -242,20 +194,7 @@ __global__ __launch_bounds__(kBlock) void fm_backward_kernel(BwdArgs a) {
   }
 }
 
-// A row of more than kFmWaveMax >= 2 kFmChunk members is the first or the last row of every chunk it
-// touches. (first row | last row if another) of chunk p; false: no such candidate.
-__device__ __forceinline__ bool fm_heavy_row(const BwdArgs& a, int64_t p, int s, int& r, int& lo, int& hi) {
-  const int64_t c_lo = p * kFmChunk, c_hi = (c_lo + kFmChunk) < a.n ? (c_lo + kFmChunk) : a.n;
-  const int ra = a.memrow[c_lo], rb = a.memrow[c_hi - 1];
-  if (s == 1 && rb == ra) return false;
-  r = s ? rb : ra;
-  if ((uint64_t)r >= (uint64_t)a.cap) return false;
-  lo = lower_bound_i32(a.memrow, 0, a.n, r);
-  hi = lower_bound_i32(a.memrow, lo, a.n, r + 1);
-  return hi - lo > kFmWaveMax;
-}
-
-// block p sums the members of chunk p that belong to a heavy row into part[(2 p + s) * W ...]
+// block p sums the members of chunk p that belong to a heavy row into part[(2 p + s) * W ...] (member_rows.h)
 template <int E, int L>
 __global__ __launch_bounds__(kBlock) void fm_backward_heavy_kernel(BwdArgs a) {
   constexpr int G = 64 / L, NG = G * (kBlock / 64);
@@ -267,7 +206,7 @@ __global__ __launch_bounds__(kBlock) void fm_backward_heavy_kernel(BwdArgs a) {
   const int64_t c_lo = p * kFmChunk, c_hi = (c_lo + kFmChunk) < a.n ? (c_lo + kFmChunk) : a.n;
   for (int s = 0; s < 2; ++s) {
     int r, lo, hi;
-    if (!fm_heavy_row(a, p, s, r, lo, hi)) continue;  // block-uniform
+    if (!member_heavy_row<kFmChunk, kFmWaveMax>(a.memrow, a.n, a.cap, p, s, r, lo, hi)) continue;  // block-uniform
     const int m0 = lo > c_lo ? lo : (int)c_lo, m1 = hi < c_hi ? hi : (int)c_hi;
     float v[E], acc[E];
     fm_row_values<E>(a, r, c0, fac, v);
@@ -292,31 +231,6 @@ __global__ __launch_bounds__(kBlock) void fm_backward_heavy_kernel(BwdArgs a) {
       a.part[(2 * p + s) * W + threadIdx.x] = t;
     }
   }
-}
-
-// the block whose chunk holds a heavy row's first member adds that row's partials in chunk order
-__global__ __launch_bounds__(64) void fm_backward_heavy_fold_kernel(BwdArgs a) {
-  const int W = a.k + 4;
-  const int64_t p = blockIdx.x;
-  const int64_t c_lo = p * kFmChunk;
-  for (int s = 0; s < 2; ++s) {
-    int r, lo, hi;
-    if (!fm_heavy_row(a, p, s, r, lo, hi)) continue;
-    if (lo < c_lo) continue;  // the row began in an earlier chunk
-    if (threadIdx.x >= W) continue;
-    const int64_t q1 = (hi - 1) / kFmChunk;
-    float t = a.part[(2 * p + s) * W + threadIdx.x];
-    for (int64_t qc = p + 1; qc <= q1; ++qc) t += a.part[(2 * qc) * W + threadIdx.x];
-    a.grad[(int64_t)r * W + threadIdx.x] = t;
-  }
-}
-
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-inline int pow2ceil(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 void check_shape(const char* op, int k, int64_t ld, int64_t cap, int64_t B, int64_t n, int blocks) {
@@ -380,9 +294,10 @@ struct BwdLaunch {
     const int grid = blocks > 0 ? blocks : grid_for(urows * L, kBlock, 8192);
     hipLaunchKernelGGL((fm_backward_kernel<E, L>), grid, kBlock, 0, s, a);
     if (n > kFmWaveMax) {
-      const int chunks = (int)((n + kFmChunk - 1) / kFmChunk);
+      const int chunks = member_chunks(n, kFmChunk);
       hipLaunchKernelGGL((fm_backward_heavy_kernel<E, L>), chunks, kBlock, 0, s, a);
-      hipLaunchKernelGGL(fm_backward_heavy_fold_kernel, chunks, 64, 0, s, a);
+      hipLaunchKernelGGL((member_heavy_fold_kernel<float, float, kFmChunk, kFmWaveMax>), chunks, 64, 0, s, a.memrow,
+                         a.n, a.cap, a.k + 4, a.part, a.grad);
     }
   }
 };
@@ -401,13 +316,12 @@ void fm_forward(const int64_t* rowptr, const int64_t* inv, const float* vals, co
 }
 
 int64_t fm_backward_part_floats(int64_t n, int W) {
-  return n > kFmWaveMax ? 2 * ((n + kFmChunk - 1) / kFmChunk) * W : 0;
+  return member_part_elems(n, W, kFmChunk, kFmWaveMax);
 }
 
 void fm_backward(const int32_t* members, const int32_t* memrow, const int32_t* rowid, const float* vals,
                  const float* dz, const float* S, const float* rows, int64_t ld, int64_t cap, int k, int64_t B,
                  int64_t n, float* grad_rows, float* part, int blocks, hipStream_t s) {
-  static_assert(kFmWaveMax >= 2 * kFmChunk, "a heavy row must be first or last in every chunk it touches");
   check_shape("fm_backward", k, ld, cap, B, n, blocks);
   if (n <= 0 || B <= 0 || cap <= 0) return;
   const int W = k + 4;

@@ -53,9 +53,8 @@
 //   delta   by the member count M of a row (found by binary search in memrow):
 //             M <= kLdaWaveMax (2048)   one wave: int32 LDS histogram of W entries, members strided over the
 //                                       lanes, then W coalesced stores;
-//             M >  kLdaWaveMax          workgroups: every kLdaChunk (1024) members of the row are counted by the
-//                                       workgroup of their chunk into int32 partials, and the workgroup that
-//                                       holds the row's first member adds the partials and stores the row.
+//             M >  kLdaWaveMax          workgroups, by the chunk rule of member_rows.h: int32 partials per
+//                                       kLdaChunk (1024) members, added in int64.
 //           Integer sums: no order can change a bit. No global atomics.
 //   loglik  one wave per document, lanes own topics as in sample, a __shfl_xor fold of the fp64 partial sums,
 //           the wave's int64 sums by two global integer atomics.

@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "lda.h"
+#include "member_rows.h"
 
 namespace minips_k {
 
@@ -312,21 +313,6 @@ struct DeltaArgs {
   int32_t* part;
 };
 
-// the first index in [lo, hi) of the ascending a with a[i] >= key (hi: none)
-__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ a, int lo, int hi, int64_t key) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int delta_unique(const DeltaArgs& a) {
-  const int64_t U = (int64_t)a.memrow[a.n - 1] + 1;
-  return (int)(U < 0 ? 0 : (U > a.cap ? a.cap : U));
-}
-
 __device__ __forceinline__ void delta_member(const DeltaArgs& a, int m, int* h) {
   const int j = a.members[m];
   if ((unsigned)j >= (unsigned)a.n) return;
@@ -346,7 +332,7 @@ __global__ __launch_bounds__(kBlock) void lda_delta_kernel(DeltaArgs a) {
   __shared__ int hist[kWaves][kLdaMaxK];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int* my = hist[wv];
-  const int U = delta_unique(a), W = a.W;
+  const int U = member_unique(a.memrow, a.n, a.cap), W = a.W;
   const i64 wave0 = (blockIdx.x * (i64)kBlock + threadIdx.x) >> 6, nwaves = ((i64)gridDim.x * kBlock) >> 6;
   const i64 ntiles = ((i64)U + kTile - 1) / kTile;
   for (i64 tile = wave0; tile < ntiles; tile += nwaves) {
@@ -371,20 +357,7 @@ __global__ __launch_bounds__(kBlock) void lda_delta_kernel(DeltaArgs a) {
   }
 }
 
-// A row of more than kLdaWaveMax >= 2 kLdaChunk members is the first or the last row of every chunk it touches.
-// (first row | last row if another) of chunk p; false: no such candidate.
-__device__ __forceinline__ bool delta_heavy_row(const DeltaArgs& a, int64_t p, int s, int& r, int& lo, int& hi) {
-  const int64_t c_lo = p * kLdaChunk, c_hi = (c_lo + kLdaChunk) < a.n ? (c_lo + kLdaChunk) : a.n;
-  const int ra = a.memrow[c_lo], rb = a.memrow[c_hi - 1];
-  if (s == 1 && rb == ra) return false;
-  r = s ? rb : ra;
-  if ((uint64_t)r >= (uint64_t)a.cap) return false;
-  lo = lower_bound_i32(a.memrow, 0, a.n, r);
-  hi = lower_bound_i32(a.memrow, lo, a.n, (int64_t)r + 1);
-  return hi - lo > kLdaWaveMax;
-}
-
-// workgroup p counts the members of chunk p that belong to a heavy row into part[(2 p + s) * W ...]
+// workgroup p counts the members of chunk p that belong to a heavy row into part[(2 p + s) * W ...] (member_rows.h)
 __global__ __launch_bounds__(kBlock) void lda_delta_heavy_kernel(DeltaArgs a) {
   __shared__ int h[kLdaMaxK];
   const int W = a.W;
@@ -392,7 +365,7 @@ __global__ __launch_bounds__(kBlock) void lda_delta_heavy_kernel(DeltaArgs a) {
   const int64_t c_lo = p * kLdaChunk, c_hi = (c_lo + kLdaChunk) < a.n ? (c_lo + kLdaChunk) : a.n;
   for (int s = 0; s < 2; ++s) {
     int r, lo, hi;
-    if (!delta_heavy_row(a, p, s, r, lo, hi)) continue;  // block-uniform
+    if (!member_heavy_row<kLdaChunk, kLdaWaveMax>(a.memrow, a.n, a.cap, p, s, r, lo, hi)) continue;  // block-uniform
     const int m0 = lo > c_lo ? lo : (int)c_lo, m1 = hi < c_hi ? hi : (int)c_hi;
     for (int k = threadIdx.x; k < W; k += kBlock) h[k] = 0;
     __syncthreads();
@@ -403,27 +376,7 @@ __global__ __launch_bounds__(kBlock) void lda_delta_heavy_kernel(DeltaArgs a) {
   }
 }
 
-// the workgroup whose chunk holds a heavy row's first member adds that row's partials and stores the row
-__global__ __launch_bounds__(kBlock) void lda_delta_fold_kernel(DeltaArgs a) {
-  const int W = a.W;
-  const int64_t p = blockIdx.x;
-  const int64_t c_lo = p * kLdaChunk;
-  for (int s = 0; s < 2; ++s) {
-    int r, lo, hi;
-    if (!delta_heavy_row(a, p, s, r, lo, hi)) continue;
-    if (lo < c_lo) continue;  // the row began in an earlier chunk
-    const int64_t q1 = (hi - 1) / kLdaChunk;
-    for (int k = threadIdx.x; k < W; k += kBlock) {
-      i64 t = a.part[(2 * p + s) * W + k];
-      for (int64_t qc = p + 1; qc <= q1; ++qc) t += a.part[(2 * qc) * W + k];
-      a.delta[(int64_t)r * W + k] = (float)t;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------- launchers
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 void check_model(const char* op, int K, double alpha, double beta, double Vbeta, int64_t ld, int64_t cap, int64_t B,
                  int64_t n, int blocks) {
   const std::string o(op);
@@ -504,12 +457,11 @@ void lda_loglik(const int64_t* rowptr, const int64_t* inv, const int16_t* z, con
 }
 
 int64_t lda_delta_part_ints(int64_t n, int W) {
-  return n > kLdaWaveMax ? 2 * ((n + kLdaChunk - 1) / kLdaChunk) * W : 0;
+  return member_part_elems(n, W, kLdaChunk, kLdaWaveMax);
 }
 
 void lda_delta(const int32_t* members, const int32_t* memrow, const int16_t* z_old, const int16_t* z_new, int64_t n,
                int K, int64_t cap, float* delta, int32_t* part, int blocks, hipStream_t stream) {
-  static_assert(kLdaWaveMax >= 2 * kLdaChunk, "a heavy row must be first or last in every chunk it touches");
   if (K < kLdaMinK || K > kLdaMaxK) throw std::runtime_error("lda_delta: K outside [2, 1024]");
   if (blocks < 0 || blocks > kLdaMaxBlocks) throw std::runtime_error("lda_delta: blocks outside [0, 65535]");
   if (n < 0 || cap < 0 || n >= (1ll << 31) || cap >= (1ll << 31))
@@ -523,9 +475,10 @@ void lda_delta(const int32_t* members, const int32_t* memrow, const int16_t* z_o
   const int grid = blocks > 0 ? blocks : grid_for(urows * 8, kBlock, 4096);
   hipLaunchKernelGGL(lda_delta_kernel, grid, kBlock, 0, stream, a);
   if (heavy) {
-    const int chunks = (int)((n + kLdaChunk - 1) / kLdaChunk);
+    const int chunks = member_chunks(n, kLdaChunk);
     hipLaunchKernelGGL(lda_delta_heavy_kernel, chunks, kBlock, 0, stream, a);
-    hipLaunchKernelGGL(lda_delta_fold_kernel, chunks, kBlock, 0, stream, a);
+    hipLaunchKernelGGL((member_heavy_fold_kernel<int32_t, int64_t, kLdaChunk, kLdaWaveMax>), chunks, kBlock, 0, stream,
+                       a.memrow, a.n, a.cap, W, a.part, a.delta);
   }
   MINIPS_HIP_CHECK(hipGetLastError());
 }

@@ -171,8 +171,6 @@ __global__ __launch_bounds__(kBlock) void adagrad_ftrl_kernel(float* table, int6
   }
 }
 
-inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 }  // namespace
 
 void sparse_adagrad_ftrl(float* table, int64_t ld, float* state, float* zn, int64_t rows, int D1, int W,

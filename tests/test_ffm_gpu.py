@@ -177,6 +177,13 @@ def test_backward_member_count_switches(F, k, how, dev):
     _check_backward(_members_case(F, k, counts, 600, seed=F + k), F, k, dev, how, blocks=(0, 2))
 
 
+@pytest.mark.parametrize("counts", [[65], [1, 65]])
+def test_backward_heavy_row_at_the_edges_of_memrow(counts, dev):
+    """The smallest heavy row as the only row (every chunk is its own, the first has no member before it) and as
+    the last row after a light one (it ends at n: the last chunk has no member after it)."""
+    _check_backward(_members_case(2, 4, counts, 20, seed=len(counts)), 2, 4, dev, blocks=(0, 2))
+
+
 @pytest.mark.parametrize("F,k", [(2, 4), (26, 16)])
 def test_backward_every_lookup_on_one_row(F, k, dev):
     _check_backward(_members_case(F, k, [5003], 1200, seed=3), F, k, dev)

@@ -219,6 +219,14 @@ def test_backward_member_count_switches(k, how, dev):
     _check_backward(_members_case(k, counts, 257, seed=k), k, dev, how, blocks=(0, 2))
 
 
+@pytest.mark.parametrize("how", ["contig", "misaligned"])
+@pytest.mark.parametrize("counts", [[2049], [1, 2049]])
+def test_backward_heavy_row_at_the_edges_of_memrow(counts, how, dev):
+    """The smallest heavy row as the only row (every chunk is its own, the first has no member before it) and as
+    the last row after a light one (it ends at n: the last chunk has no member after it)."""
+    _check_backward(_members_case(4, counts, 40, seed=len(counts)), 4, dev, how, blocks=(0, 2))
+
+
 @pytest.mark.parametrize("k", [8, 32])
 def test_backward_every_lookup_on_one_row(k, dev):
     _check_backward(_members_case(k, [5003], 40, seed=3), k, dev)

@@ -111,12 +111,14 @@ def test_out_of_range_rows_and_topics_are_skipped(K, dev):
 
 
 # ------------------------------------------------------------------------------ delta
-def delta_case(K, seed=0):
-    """Rows by member count: 3000 and 2500 (two rows of the chunked workgroup path, side by side, so chunks hold
-    the end of one and the start of the other), 100, 2048 (the last of the wave path), 2049 (the first of the
-    chunked one), then 40 rows of one member, shuffled over the tokens. Two more rows have no member."""
+HEAVY_COUNTS = [3000, 2500, 100, 2048, 2049] + [1] * 40
+
+
+def delta_case(K, seed=0, counts=HEAVY_COUNTS):
+    """Rows by member count. HEAVY_COUNTS: 3000 and 2500 (two rows of the chunked workgroup path, side by side, so
+    chunks hold the end of one and the start of the other), 100, 2048 (the last of the wave path), 2049 (the first
+    of the chunked one), then 40 rows of one member, shuffled over the tokens. Two more rows have no member."""
     g = torch.Generator().manual_seed(seed + K)
-    counts = [3000, 2500, 100, 2048, 2049] + [1] * 40
     inv = torch.repeat_interleave(torch.arange(len(counts)), torch.tensor(counts))
     inv = inv[torch.randperm(inv.numel(), generator=g)]
     n = inv.numel()
@@ -131,7 +133,20 @@ def delta_case(K, seed=0):
 @pytest.mark.parametrize("init", [False, True])
 @pytest.mark.parametrize("K", [3, 70, 1024])
 def test_delta_equals_the_cpu_on_every_path(K, init, blocks, dev):
-    inv, z_old, z_new, cap = delta_case(K)
+    check_delta(K, init, blocks, dev, HEAVY_COUNTS)
+
+
+@pytest.mark.parametrize("blocks", [0, 2])
+@pytest.mark.parametrize("init", [False, True])
+@pytest.mark.parametrize("counts", [[2049], [1, 2049]])
+def test_delta_heavy_row_at_the_edges_of_memrow(counts, init, blocks, dev):
+    """The smallest row of the chunked path as the only row (every chunk is its own, the first has no member before
+    it) and as the last row after a light one (it ends at n: the last chunk has no member after it)."""
+    check_delta(3, init, blocks, dev, counts)
+
+
+def check_delta(K, init, blocks, dev, counts):
+    inv, z_old, z_new, cap = delta_case(K, counts=counts)
     W = (K + 3) & ~3
     if init:
         z_old = None
