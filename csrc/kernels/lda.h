@@ -76,6 +76,18 @@ constexpr int kLdaLoglikBits = 24;      // the log likelihood counts units of 2^
 constexpr int kLdaWaveMax = 2048;       // members of a row one wave counts; more go to the chunked workgroups
 constexpr int kLdaChunk = 1024;         // members per workgroup of the chunked path (kLdaWaveMax >= 2 kLdaChunk)
 
+// mix and mulhi_u64 of the rule (the negative sampler of sgns.h draws with them too)
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+__device__ __forceinline__ uint64_t mulhi_u64(uint64_t a, uint64_t b) { return __umul64hi(a, b); }
+
 // int32 partials the chunked path of lda_delta needs for n members and rows of W columns (0: none)
 int64_t lda_delta_part_ints(int64_t n, int W);
 

@@ -18,15 +18,6 @@ constexpr int kWaves = kBlock / kWave;
 typedef unsigned long long u64;
 typedef long long i64;
 
-__device__ __forceinline__ u64 mix64(u64 x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 __device__ __forceinline__ u64 sweep_base(u64 seed, u64 it) { return mix64(seed + it * 0x9E3779B97F4A7C15ull); }
 
 __device__ __forceinline__ u64 draw(u64 base, i64 g, i64 j) { return mix64(base ^ ((u64)g * 4096ull + (u64)j)); }

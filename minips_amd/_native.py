@@ -26,6 +26,8 @@
   ``gbdt_split`` / ``gbdt_leaf`` / ``gbdt_advance`` / ``gbdt_predict``): a tenth small torch extension, same rule.
 * ``_ldak``     -- the fixed-point LDA collapsed Gibbs kernels (``ops.lda_sample`` / ``lda_delta`` /
   ``lda_loglik``): an eleventh small torch extension, same rule.
+* ``_w2vk``     -- the word2vec skip-gram negative-sampling kernels (``ops.sgns_lookups`` / ``sgns_forward`` /
+  ``sgns_backward``): a twelfth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -116,6 +118,11 @@ def ldak():
     return _load("_ldak", "gfx950 HIP LDA Gibbs kernels")
 
 
+def w2vk():
+    """Return the HIP word2vec (skip-gram, negative sampling) kernel module or raise a loud error."""
+    return _load("_w2vk", "gfx950 HIP word2vec skip-gram negative-sampling kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -163,6 +170,10 @@ def gbdtk_available() -> bool:
 
 def ldak_available() -> bool:
     return _available(ldak)
+
+
+def w2vk_available() -> bool:
+    return _available(w2vk)
 
 
 def native_dir() -> str:

@@ -340,3 +340,33 @@ class LDASynth:
     def block_of(self, words: torch.Tensor) -> torch.Tensor:
         """The planted topic whose block holds each word (words past the last block: the last topic)."""
         return (words // self.block).clamp(max=self.topics - 1)
+
+
+class W2VSynth:
+    """A corpus with planted word groups for word2vec (models/word2vec.py): group k owns the word block
+    [k * words_per_group, (k + 1) * words_per_group). Each of the ``sentences`` sentences of ``length`` tokens picks
+    a group uniformly; each token comes uniformly from that group's block with probability 1 - ``noise``, else
+    uniformly from the whole vocabulary. corpus() returns (tokens int64 [sentences * length], sent_rowptr int64
+    [sentences + 1]). Generated on the host from ``seed`` alone."""
+
+    def __init__(self, groups: int = 8, words_per_group: int = 16, sentences: int = 512, length: int = 16,
+                 noise: float = 0.1, seed: int = 0):
+        if groups < 1 or words_per_group < 1 or sentences < 1 or length < 1 or not 0 <= noise <= 1:
+            raise ValueError(f"W2VSynth: groups {groups}, words_per_group {words_per_group}, sentences {sentences}, "
+                             f"length {length}, noise {noise}")
+        self.groups, self.words_per_group, self.sentences, self.length = groups, words_per_group, sentences, length
+        self.vocab = groups * words_per_group
+        gen = torch.Generator()
+        gen.manual_seed(seed + 1)
+        self.group = torch.randint(groups, (sentences,), generator=gen)
+        own = self.group[:, None] * words_per_group + torch.randint(words_per_group, (sentences, length), generator=gen)
+        anyw = torch.randint(self.vocab, (sentences, length), generator=gen)
+        noisy = torch.rand(sentences, length, generator=gen, dtype=torch.float64) < noise
+        self.tokens = torch.where(noisy, anyw, own).reshape(-1)
+        self.rowptr = torch.arange(sentences + 1, dtype=torch.int64) * length
+
+    def corpus(self):
+        return self.tokens, self.rowptr
+
+    def counts(self) -> torch.Tensor:
+        return torch.bincount(self.tokens, minlength=self.vocab)

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, ldak, optk, wdftrlk
+from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, ldak, optk, w2vk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1649,6 +1649,195 @@ def lda_loglik(rowptr, inv, z, rows, nk, alpha, beta, Vbeta, acc, blocks=0):
         acc[0] += torch.round(-torch.log(p) * LDA_LOGLIK_SCALE).to(torch.int64).sum()
     acc[1] += t.numel()
     return acc
+
+
+# ----------------------------------------------------------------------------- word2vec: skip-gram, negative sampling
+SGNS_MIN_DIM, SGNS_MAX_DIM, SGNS_MAX_NEG = 4, 512, 64  # csrc/kernels/sgns.h (the binding exports them too)
+SGNS_MAX_TOKENS = 1 << 40
+SGNS_Q_SCALE = float(1 << 20)
+_SGNS_ROWS = 1 << 13  # pairs per pass of the CPU references
+
+
+def _sgns_check(op, d, N, rows, blocks=0):
+    if d % 4 or not SGNS_MIN_DIM <= d <= SGNS_MAX_DIM:
+        raise RuntimeError(f"{op}: rows are {d} wide, expected d % 4 == 0 and {SGNS_MIN_DIM} <= d <= {SGNS_MAX_DIM}")
+    if not 1 <= N <= SGNS_MAX_NEG:
+        raise RuntimeError(f"{op}: N is {N}, expected 1 <= N <= {SGNS_MAX_NEG}")
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise RuntimeError(f"{op}: rows must be fp32 [cap, d], got {rows.dtype} {tuple(rows.shape)}")
+    if not 0 <= blocks <= 65535:
+        raise RuntimeError(f"{op}: blocks is {blocks}, expected 0 <= blocks <= 65535")
+
+
+def sgns_alias(counts):
+    """The integer alias table of word2vec's negative sampler (the rule: csrc/kernels/sgns.h), built on the host
+    with Python integers in a fixed order from the int64 word counts [V]: q_w = c_w > 0 ? max(1, rint(c_w^0.75
+    2^20)) : 0 in fp64, T = sum q_w, Vose's method over V buckets of capacity T with the masses q_w V. Returns
+    (thr int64 [V], alias int32 [V], T, q): thr[w] + sum_{i: alias[i] == w} (T - thr[i]) == q_w V exactly."""
+    c = counts.detach().to("cpu", torch.int64).reshape(-1)
+    V = c.numel()
+    if V < 1 or V >= 1 << 31 or bool((c < 0).any()):
+        raise ValueError(f"w2v: {V} word counts, expected 1 <= V < 2^31 and no negative count")
+    if int(c.sum()) >= SGNS_MAX_TOKENS:
+        raise ValueError(f"w2v: the counts hold {int(c.sum())} tokens, expected fewer than 2^40")
+    qt = torch.where(c > 0, torch.round(c.double().pow(0.75) * SGNS_Q_SCALE).clamp_(min=1.0),
+                     torch.zeros((), dtype=torch.float64))
+    q = [int(v) for v in qt.to(torch.int64).tolist()]
+    T = sum(q)
+    if T < 1:
+        raise ValueError("w2v: every word count is 0: there is nothing to draw negatives from")
+    m = [v * V for v in q]
+    thr, alias = [T] * V, list(range(V))
+    small = [w for w in range(V) if m[w] < T]
+    large = [w for w in range(V) if m[w] >= T]
+    while small and large:
+        s, big = small.pop(), large[-1]
+        thr[s], alias[s] = m[s], big
+        m[big] -= T - m[s]
+        if m[big] < T:
+            large.pop()
+            small.append(big)
+    assert not small and all(m[w] == T for w in large)  # integers: what is left fills its bucket exactly
+    return torch.tensor(thr, dtype=torch.int64), torch.tensor(alias, dtype=torch.int32), T, q
+
+
+def sgns_keep(counts, sample: float) -> torch.Tensor:
+    """word2vec's subsampling as integers: int64 [V] holding uint32 thresholds kt; a token of word w with the
+    32-bit draw x is kept iff x <= kt[w]. kt = min(2^32 - 1, floor(p 2^32)) with p = min(1, (sqrt(f / s) + 1) s / f)
+    in fp64, f = c_w / sum c; ``sample`` 0 (and a word of count 0) keeps everything."""
+    c = counts.detach().to("cpu", torch.int64).reshape(-1).double()
+    full = float((1 << 32) - 1)
+    if not sample > 0:
+        return torch.full((c.numel(),), (1 << 32) - 1, dtype=torch.int64)
+    f = c / c.sum().clamp(min=1.0)
+    p = torch.where(f > 0, (torch.sqrt(f / sample) + 1.0) * sample / f.clamp(min=1e-300), torch.ones_like(f))
+    return torch.floor(p.clamp(max=1.0) * float(1 << 32)).clamp_(max=full).to(torch.int64)
+
+
+def sgns_lookups(centres, contexts, thr, alias, T, seed, epoch, pair_base, N, negatives=None):
+    """The int64 key matrix [P, N + 2] of P skip-gram pairs (csrc/kernels/sgns.h): column 0 is 2 c (the centre's
+    input row), column 1 is 2 o + 1 (the context's output row), column 2 + t is 2 neg + 1, where neg is draw t of the
+    global pair pair_base + p in ``epoch`` from the alias table (thr int64 [V] holding uint64 bits, alias int32 [V],
+    T), or negatives[p, t] when the explicit int32 [P, N] ``negatives`` are given. A word outside [0, V) gives the
+    key -1. One launch on the GPU; the CPU path is the same integer arithmetic on int64 tensors."""
+    N, T, P, V = int(N), int(T), centres.numel(), thr.numel()
+    if _gpu(centres):
+        keys = torch.empty(P, N + 2, dtype=torch.int64, device=centres.device)
+        w2vk().sgns_lookups(centres, contexts, thr, alias, T, int(seed), int(epoch), int(pair_base), N, negatives, keys)
+        return keys
+    if not 1 <= N <= SGNS_MAX_NEG or not 1 <= V < 1 << 31 or alias.numel() != V or contexts.numel() != P or \
+            not 1 <= T < 1 << 59 or epoch < 0 or pair_base < 0:
+        raise RuntimeError(f"sgns_lookups: N {N}, V {V}, alias [{alias.numel()}], contexts [{contexts.numel()}] for "
+                           f"{P} centres, T {T}, epoch {epoch}, pair_base {pair_base}")
+    if negatives is None:
+        base = lda_mix_int(int(seed) + int(epoch) * _LDA_GOLD)
+        g = torch.arange(P, dtype=torch.int64) + int(pair_base)
+        r = _lda_mix((g[:, None] * 64 + torch.arange(N, dtype=torch.int64)[None, :]) ^ _lda_s64(base))
+        i = mulhi_u64(r, torch.full_like(r, V))
+        x = mulhi_u64(_lda_mix(r), torch.full_like(r, T))
+        neg = torch.where(x < thr[i], i, alias[i].long())
+    else:
+        if tuple(negatives.shape) != (P, N):
+            raise RuntimeError(f"sgns_lookups: negatives {tuple(negatives.shape)}, expected [{P}, {N}]")
+        neg = negatives.long()
+    words = torch.cat([centres.long().reshape(P, 1), contexts.long().reshape(P, 1), neg], 1)
+    odd = torch.ones(N + 2, dtype=torch.int64)
+    odd[0] = 0
+    return torch.where((words >= 0) & (words < V), 2 * words + odd, torch.full_like(words, -1))
+
+
+def _sgns_head(s, first, gscale):
+    """member_rows.h's logistic head on fp32 tensors: (e, loss) of the logits s against y = ``first``."""
+    ex = torch.exp(-s.abs())
+    big, small = 1.0 / (1.0 + ex), ex / (1.0 + ex)
+    sg, one_m = torch.where(s >= 0, big, small), torch.where(s >= 0, small, big)
+    e = torch.where(first, -one_m, sg) * torch.tensor(float(gscale), dtype=torch.float32)
+    loss = s.clamp(min=0) - torch.where(first, s, torch.zeros_like(s)) + torch.log1p(ex)
+    return e, loss
+
+
+def sgns_forward(inv, rows, N, gscale=1.0, blocks=0):
+    """Skip-gram with negative sampling over pulled rows (the rule: csrc/kernels/sgns.h). inv int64 [P (N + 2)] are a
+    plan's row indices of sgns_lookups' keys, rows fp32 [cap, d]. Pair p has the centre row a = inv[p (N + 2)] and
+    the targets t = 0 .. N with rows b_t = inv[p (N + 2) + 1 + t], y_t = [t == 0]; a target t >= 1 with b_t == b_0 is
+    masked, a row index outside [0, cap) makes its target (or, for the centre, the whole pair) not exist. Returns
+    fp32 (e [P, N + 1], loss [P], h [P, d]): s_t = <rows[a], rows[b_t]>, e_t = (sigmoid(s_t) - y_t) gscale (exactly 0
+    when masked), loss = the sum of the live targets' logistic losses, h = sum_t e_t rows[b_t]. One fused gfx950
+    launch on the GPU (no atomics, the same bits for every grid size, ``blocks``); the CPU path is the fp32
+    PyTorch reference of the same rule."""
+    N = int(N)
+    K2 = N + 2
+    P, d = inv.numel() // K2, rows.shape[1] if rows.dim() == 2 else 0
+    if _gpu(rows):
+        dev = rows.device
+        e = torch.empty(P, N + 1, dtype=torch.float32, device=dev)
+        loss = torch.empty(P, dtype=torch.float32, device=dev)
+        h = torch.empty(P, d, dtype=torch.float32, device=dev)
+        w2vk().sgns_forward(inv, rows, N, float(gscale), e, loss, h, int(blocks))
+        return e, loss, h
+    _sgns_check("sgns_forward", d, N, rows, blocks)
+    if inv.numel() != P * K2:
+        raise RuntimeError(f"sgns_forward: inv holds {inv.numel()} lookups, not a multiple of N + 2 = {K2}")
+    cap = rows.shape[0]
+    e = torch.zeros(P, N + 1, dtype=torch.float32)
+    loss = torch.zeros(P, dtype=torch.float32)
+    h = torch.zeros(P, d, dtype=torch.float32)
+    if P == 0 or cap == 0:
+        return e, loss, h
+    iv = inv.view(P, K2)
+    first = torch.zeros(1, N + 1, dtype=torch.bool)
+    first[0, 0] = True
+    for lo in range(0, P, _SGNS_ROWS):
+        a, b = iv[lo:lo + _SGNS_ROWS, 0], iv[lo:lo + _SGNS_ROWS, 1:]
+        ok = ((a >= 0) & (a < cap))[:, None] & (b >= 0) & (b < cap)
+        ok[:, 1:] &= b[:, 1:] != b[:, :1]
+        va, u = rows[a.clamp(0, cap - 1)], rows[b.clamp(0, cap - 1)]
+        ee, ll = _sgns_head((va[:, None, :] * u).sum(-1), first, gscale)
+        ee = torch.where(ok, ee, torch.zeros_like(ee))
+        e[lo:lo + _SGNS_ROWS] = ee
+        loss[lo:lo + _SGNS_ROWS] = torch.where(ok, ll, torch.zeros_like(ll)).sum(1)
+        h[lo:lo + _SGNS_ROWS] = (ee[:, :, None] * u).sum(1)
+    return e, loss, h
+
+
+def sgns_backward(inv, e, h, rows, N, grad_rows, csr=None, blocks=0):
+    """Gradient of every unique pulled row of sgns_forward's batch (csrc/kernels/sgns.h): over the lookups j of row
+    r (inv[j] == r), p = j // (N + 2), col = j % (N + 2), grad_rows[r] = sum of h[p] (col == 0) or e[p, col - 1] *
+    rows[inv[p (N + 2)]] (col >= 1); rows without lookups are left untouched. ``csr`` = (members, memrow): the
+    lookups grouped by unique row (a plan's lookup CSR; built from ``inv`` here when absent on the GPU, ignored on
+    the CPU). On the GPU every such row is written exactly once in a fixed summation order -- no atomics, the same
+    bits on every run and for every grid size (``blocks``); the CPU reference sums with index_add_ over ``inv``."""
+    N = int(N)
+    K2 = N + 2
+    if _gpu(rows):
+        if csr is None:  # (not the model's path) rows outside [0, cap) go to a row past the end, which the kernel
+            cap = rows.shape[0]  # ignores: emb_build_csr trusts its rows
+            ok = (inv >= 0) & (inv < cap)
+            csr = emb_build_csr(torch.where(ok, inv, torch.full_like(inv, cap)), 1, cap + 1)
+        w2vk().sgns_backward(csr[0], csr[1], inv, e, h, rows, N, grad_rows, int(blocks))
+        return grad_rows
+    P, d = h.shape[0], h.shape[1]
+    _sgns_check("sgns_backward", d, N, rows, blocks)
+    cap = rows.shape[0]
+    if inv.numel() != P * K2 or tuple(e.shape) != (P, N + 1) or rows.shape[1] < d or grad_rows.dim() != 2 or \
+            grad_rows.shape[1] != d or grad_rows.shape[0] < cap:
+        raise RuntimeError(f"sgns_backward: inv [{inv.numel()}], e {tuple(e.shape)}, h {tuple(h.shape)}, rows "
+                           f"{tuple(rows.shape)}, grad_rows {tuple(grad_rows.shape)} for {P} pairs of {K2} lookups")
+    if P == 0 or cap == 0:
+        return grad_rows
+    iv = inv.view(P, K2)
+    acc = torch.zeros(cap, d, dtype=torch.float32)
+    for lo in range(0, P, _SGNS_ROWS):
+        a, b = iv[lo:lo + _SGNS_ROWS, 0], iv[lo:lo + _SGNS_ROWS, 1:]
+        cen = (a >= 0) & (a < cap)
+        acc.index_add_(0, a[cen], h[lo:lo + _SGNS_ROWS][cen])
+        ok = cen[:, None] & (b >= 0) & (b < cap)
+        va = rows[a.clamp(0, cap - 1)][:, :d]
+        acc.index_add_(0, b[ok], (e[lo:lo + _SGNS_ROWS][:, :, None] * va[:, None, :])[ok])
+    touched = torch.zeros(cap, dtype=torch.bool)
+    touched[inv[(inv >= 0) & (inv < cap)]] = True
+    grad_rows[:cap][touched] = acc[touched]
+    return grad_rows
 
 
 # ----------------------------------------------------------------------------- optimizers

@@ -1371,6 +1371,15 @@ class SparseTable:
         table, index, base = self._serve_index(plan)
         return plan, table, index, base
 
+    def zero_rows(self, keys: torch.Tensor):
+        """Sets the rows of ``keys`` that this rank holds to zero (initialisation, before the first clock; the
+        optimizer state is left alone). Keys of other ranks' ranges are ignored: every rank calls it with the same
+        keys."""
+        rows = self._route_keys(keys.reshape(-1).to(self.shard.device, torch.int64))
+        mine = rows[(rows >= self.base) & (rows < self.base + self.rows_local)] - self.base
+        self.shard[mine] = 0
+        return self
+
     def get_rows(self, keys: torch.Tensor) -> torch.Tensor:
         """Reference-style Get: the values of every requested key, in request order."""
         rows, plan = self.get(keys)

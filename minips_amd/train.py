@@ -24,6 +24,11 @@ sweeps over a resident corpus -- --lda_docs synthetic documents of --lda_doc_len
 or an --input libsvm file whose lines are documents (`label word:count ...`, the label is ignored);
 --lda_topics / --lda_alpha / --lda_beta / --lda_vocab, --batch documents per clock; the reported loss is the
 negative per-token log likelihood; the final JSON gains lda_topics, lda_tokens and lda_loglik, collective BSP only.
+--model w2v is word2vec by skip-gram with negative sampling (models/word2vec.py): --steps counts epochs over a
+resident corpus -- --w2v_sentences synthetic sentences of --w2v_len tokens over all ranks (W2VSynth), or an --input
+libsvm file whose lines are sentences in file order (`label word:x ...`, ids minus one, values ignored);
+--w2v_dim / --w2v_negatives / --w2v_window / --w2v_sample / --w2v_vocab, --batch pairs per clock; the reported loss
+is the epoch's mean pair loss; the final JSON gains w2v_dim, w2v_pairs and (synthetic) w2v_purity, collective only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -49,7 +54,7 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm", "dcn", "ffm", "gbdt", "lda"])
+                                                             "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -175,6 +180,19 @@ def parse(argv=None):
                     help="lda, synthetic data: documents over all ranks (default 256 with --small, else 65536)")
     ap.add_argument("--lda_doc_len", type=int, default=None,
                     help="lda, synthetic data: tokens per document, 1..4096 (default 48 with --small, else 128)")
+    ap.add_argument("--w2v_dim", type=int, default=None, help="w2v: vector width, a multiple of 4 in [4, 512] "
+                                                              "(default 16 with --small, else 128)")
+    ap.add_argument("--w2v_negatives", type=int, default=None, help="w2v: negatives per pair, 1..64 (default 5)")
+    ap.add_argument("--w2v_window", type=int, default=None, help="w2v: the largest window, 1..64 (default 5)")
+    ap.add_argument("--w2v_sample", type=float, default=None,
+                    help="w2v: subsampling threshold in [0, 1), 0 keeps every token (default 1e-3)")
+    ap.add_argument("--w2v_vocab", type=int, default=None,
+                    help="w2v: vocabulary size (synthetic default: 128 with --small, else 65536, a multiple of the 8 / "
+                         "256 planted groups; with --input: the largest word id over all ranks + 1)")
+    ap.add_argument("--w2v_sentences", type=int, default=None,
+                    help="w2v, synthetic data: sentences over all ranks (default 512 with --small, else 262144)")
+    ap.add_argument("--w2v_len", type=int, default=None,
+                    help="w2v, synthetic data: tokens per sentence (default 16 with --small, else 32)")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -288,6 +306,50 @@ def parse(argv=None):
             ap.error("--model lda: no table checkpoints (they do not hold the topic of every token)")
     elif lda_flags:
         ap.error(f"{' / '.join(lda_flags)}: --model lda only, not {args.model}")
+    w2v_flags = [f"--{k}" for k in ("w2v_dim", "w2v_negatives", "w2v_window", "w2v_sample", "w2v_vocab",
+                                    "w2v_sentences", "w2v_len") if getattr(args, k) is not None]
+    if args.model == "w2v":
+        args.w2v_dim = (16 if args.small else 128) if args.w2v_dim is None else args.w2v_dim
+        args.w2v_negatives = 5 if args.w2v_negatives is None else args.w2v_negatives
+        args.w2v_window = 5 if args.w2v_window is None else args.w2v_window
+        args.w2v_sample = 1e-3 if args.w2v_sample is None else args.w2v_sample
+        if args.w2v_dim % 4 or not 4 <= args.w2v_dim <= 512:
+            ap.error(f"--model w2v: --w2v_dim {args.w2v_dim} must be a multiple of 4 in [4, 512]")
+        if not 1 <= args.w2v_negatives <= 64:
+            ap.error(f"--model w2v: --w2v_negatives {args.w2v_negatives} must be in [1, 64]")
+        if not 1 <= args.w2v_window <= 64:
+            ap.error(f"--model w2v: --w2v_window {args.w2v_window} must be in [1, 64]")
+        if not 0 <= args.w2v_sample < 1:
+            ap.error(f"--model w2v: --w2v_sample {args.w2v_sample} must be in [0, 1)")
+        if args.input and (args.w2v_sentences is not None or args.w2v_len is not None):
+            ap.error("--model w2v: --w2v_sentences / --w2v_len size the synthetic corpus, not an --input file")
+        if not args.input:
+            args.w2v_vocab = (128 if args.small else 65536) if args.w2v_vocab is None else args.w2v_vocab
+            args.w2v_sentences = (512 if args.small else 262144) if args.w2v_sentences is None else args.w2v_sentences
+            args.w2v_len = (16 if args.small else 32) if args.w2v_len is None else args.w2v_len
+            groups = 8 if args.small else 256
+            if args.w2v_sentences < 1 or args.w2v_len < 1:
+                ap.error("--model w2v: --w2v_sentences and --w2v_len must be >= 1")
+            if args.w2v_vocab < groups or args.w2v_vocab % groups:
+                ap.error(f"--model w2v: --w2v_vocab {args.w2v_vocab} must be a positive multiple of the {groups} "
+                         f"planted groups of the synthetic corpus")
+        if args.w2v_vocab is not None and not 1 <= args.w2v_vocab < 1 << 30:
+            ap.error(f"--model w2v: --w2v_vocab {args.w2v_vocab} must be in [1, 2^30)")
+        if args.batch < 0 or args.batch * (args.w2v_negatives + 2) >= 1 << 31:
+            ap.error(f"--model w2v: --batch {args.batch} pairs per clock must be >= 1 (0: 65536) with batch * "
+                     f"(negatives + 2) < 2^31")
+        if args.transport == "onesided":
+            ap.error("--model w2v needs --transport collective (no w2v on the one-sided transport, SSP / ASP "
+                     "included)")
+        if args.kStorageType != "vector":
+            ap.error("--model w2v needs --kStorageType Vector (no w2v on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model w2v keeps float32 rows, not --value_dtype {args.value_dtype}")
+        if args.eval_every > 0:
+            ap.error("--model w2v: no --eval_every (there is no held-out split of a corpus; the loss is the epoch's "
+                     "mean pair loss)")
+    elif w2v_flags:
+        ap.error(f"{' / '.join(w2v_flags)}: --model w2v only, not {args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -635,6 +697,49 @@ def build(args, comm):
             return torch.tensor([-m.loglik() if report else 0.0], device=dev)
 
         return m, {}, (lambda: _Resident(None)), lda_step, 1
+    if args.model == "w2v":
+        from .models.word2vec import Word2Vec, Word2VecConfig
+
+        if args.input:  # every line a sentence, its words in file order (label and values ignored); this rank's lines
+            shard = args._shard
+            rp, words = shard.rowptr.long().cpu(), shard.cols.long().cpu()
+            t = torch.zeros(comm.world + 1, dtype=torch.int64, device=dev)
+            t[comm.rank] = words.numel()
+            comm.all_reduce_(t)  # the tokens of the ranks before this one: the global token positions
+            base = int(t[: comm.rank].sum())
+            vmax = torch.tensor([int(words.max()) + 1 if words.numel() else 1], dtype=torch.int64, device=dev)
+            comm.all_reduce_(vmax, op=dist.ReduceOp.MAX)
+            V = args.w2v_vocab if args.w2v_vocab is not None else int(vmax)
+            if words.numel() and int(words.max()) >= V:
+                raise ValueError(f"w2v: the input holds the word id {int(words.max()) + 1}, --w2v_vocab is {V}")
+            args._w2v_group = 0
+        else:  # one corpus for every rank (seed), this rank's even slice of its sentences
+            from .data.synthetic import W2VSynth
+            from .ps.tables import even_bounds
+
+            groups = 8 if args.small else 256
+            V = args.w2v_vocab
+            synth = W2VSynth(groups, V // groups, args.w2v_sentences, args.w2v_len, seed=args.seed)
+            b = even_bounds(args.w2v_sentences, comm.world)
+            lo, hi = b[comm.rank], b[comm.rank + 1]
+            base = int(synth.rowptr[lo])
+            rp = synth.rowptr[lo:hi + 1] - base
+            words = synth.tokens[base:int(synth.rowptr[hi])]
+            args._w2v_group = V // groups
+        m = Word2Vec(Word2VecConfig(vocab=V, dim=args.w2v_dim, negatives=args.w2v_negatives, window=args.w2v_window,
+                                    sample=args.w2v_sample, lr=args.alpha, batch_pairs=args.batch or 65536,
+                                    seed=args.seed, consistency=args.consistency, staleness=args.staleness), comm)
+        counts = torch.bincount(words, minlength=V).to(dev)
+        comm.all_reduce_(counts)
+        m.set_counts(counts)
+        m.attach(words, rp, base)
+
+        class _Epochs(_Resident):  # a restart at iteration k resumes with epoch k's draws
+            def skip(self, k: int):
+                m.epochs = k
+
+        # epoch() returns the epoch's mean pair loss over all ranks (collective, read on the host once an epoch)
+        return m, {0: m.table}, (lambda: _Epochs(None)), (lambda _: torch.tensor([m.epoch()], device=dev)), 1
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
         # shard stays resident in HBM and batches are consecutive rows, cut on the device
@@ -856,7 +961,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda") and args.input:
+    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda", "w2v") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -1098,6 +1203,12 @@ def main(argv=None):
     if args.model == "lda":  # the topic totals are replicated: their sum is the corpus's token count
         sums = model.nk.double().sum().reshape(1)
         ftrl_final.update(lda_topics=model.K, lda_tokens=int(model.nk.sum()), lda_loglik=round(model.loglik(), 6))
+    if args.model == "w2v":  # vectors() is a collective Get; the purity of the planted groups is read on the host
+        ftrl_final.update(w2v_dim=model.d, w2v_pairs=model.total_pairs)
+        if args._w2v_group:
+            from .models.word2vec import purity
+
+            ftrl_final["w2v_purity"] = round(purity(model.vectors(), args._w2v_group), 6)
     if args.sparse_optimizer == "ftrl":  # a collective: every rank counts its shard
         ftrl_final = dict(nnz=model.nnz(), sparse_optimizer="ftrl")
     if args.wide_optimizer == "ftrl" and args.model in ("fm", "ffm"):  # likewise a collective

@@ -14,7 +14,8 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         WideDeepConfig(cross_layers=L)), ffm (the field-aware FM, --ffm_fields x 262144 features, --ffm_k),
         gbdt (a boosting round of the fixed-point histogram GBDT over --batch resident samples per rank; --gbdt_depth,
         --gbdt_bins, --gbdt_features; ms_per_step is ms per tree), lda (a sweep of the fixed-point collapsed Gibbs
-        sampler over --batch resident tokens per rank; --lda_topics; ms_per_step is ms per sweep).
+        sampler over --batch resident tokens per rank; --lda_topics; ms_per_step is ms per sweep), w2v (a clock of
+        word2vec skip-gram with negative sampling on --batch pairs of Zipf words; --w2v_dim, --w2v_negatives).
 """
 from __future__ import annotations
 
@@ -189,6 +190,28 @@ def build(args, comm):
         return m, sweep, words.numel(), "tokens/s", \
             dict(model=f"LDA collapsed Gibbs, {args.lda_topics} topics, 65536 words, {words.numel()} resident tokens "
                        f"per rank, clocks of 8192 documents, int64 fixed-point weights", seq_len=None)
+    if args.model == "w2v":
+        from minips_amd.models.word2vec import Word2Vec, Word2VecConfig
+        from tools.bench_fm import draw_keys
+
+        # a clock on --batch explicit pairs (default 65536) of Zipf(1.05) words over 2^20 words, the negatives drawn
+        # from the unigram^0.75 of the same law; a ring of ready pair batches (pair generation is epoch()'s job)
+        B, V = args.batch or 65536, 1 << 20
+        gen = torch.Generator(device=dev).manual_seed(1000 + r)
+        m = Word2Vec(Word2VecConfig(vocab=V, dim=args.w2v_dim, negatives=args.w2v_negatives, batch_pairs=B,
+                                    consistency=args.consistency, staleness=args.staleness), comm)
+        m.set_counts(torch.bincount(draw_keys("zipf", 1 << 24, V, 1.05, torch.Generator(device=dev).manual_seed(7),
+                                              dev), minlength=V) + 1)
+        ring = [(draw_keys("zipf", B, V, 1.05, gen, dev), draw_keys("zipf", B, V, 1.05, gen, dev)) for _ in range(4)]
+        at = [0]
+
+        def step():
+            at[0] += 1
+            return m.train_step(*ring[at[0] % len(ring)], pair_base=(at[0] * comm.world + r) * B)
+
+        return m, step, B, "pairs/s", \
+            dict(model=f"word2vec skip-gram, {args.w2v_negatives} negatives, {V} words, fp32 rows of {args.w2v_dim}, "
+                       f"Zipf(1.05) words", seq_len=None)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -267,7 +290,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
                                                          "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
-                                                         "gbdt", "lda"])
+                                                         "gbdt", "lda", "w2v"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -308,6 +331,9 @@ def main():
     ap.add_argument("--gbdt_depth", "--gbdt-depth", dest="gbdt_depth", type=int, default=6, help="gbdt: tree depth")
     ap.add_argument("--gbdt_bins", "--gbdt-bins", dest="gbdt_bins", type=int, default=64, help="gbdt: bins")
     ap.add_argument("--lda_topics", "--lda-topics", dest="lda_topics", type=int, default=256, help="lda: topics")
+    ap.add_argument("--w2v_dim", "--w2v-dim", dest="w2v_dim", type=int, default=128, help="w2v: vector width")
+    ap.add_argument("--w2v_negatives", "--w2v-negatives", dest="w2v_negatives", type=int, default=5,
+                    help="w2v: negatives per pair")
     ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
                     help="gbdt: features (the teacher reads 5)")
     args = ap.parse_args()

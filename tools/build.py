@@ -29,6 +29,8 @@ Targets
             tenth small torch extension, over k_gbdt.o only)
   lda_py    csrc/bindings/lda_py.cpp     -> minips_amd/_ldak*.so     (the fixed-point LDA Gibbs kernels: an
             eleventh small torch extension, over k_lda.o only)
+  sgns_py   csrc/bindings/sgns_py.cpp    -> minips_amd/_w2vk*.so    (the word2vec skip-gram negative-sampling
+            kernels: a twelfth small torch extension, over k_sgns.o only)
   san_thread / san_address   runtime + runtime_test + apps built with -fsanitize=thread|address
             (host code only) -> build/san_<kind>/bin/ (race detection on the runtime)
 
@@ -282,6 +284,11 @@ def build_lda_py(kobjs: list[str]) -> str:
     return _build_small_ext(kobjs, "lda_py", "_ldak", "k_lda.o")
 
 
+def build_sgns_py(kobjs: list[str]) -> str:
+    """minips_amd/_w2vk: the word2vec skip-gram negative-sampling binding over k_sgns.o alone."""
+    return _build_small_ext(kobjs, "sgns_py", "_w2vk", "k_sgns.o")
+
+
 def build_sanitized(kind: str) -> list[str]:
     """The CPU runtime, its unit/integration tests and the apps under a sanitizer."""
     d = os.path.join(BUILD, f"san_{kind}")
@@ -310,7 +317,7 @@ def build_sanitized(kind: str) -> list[str]:
 def main(argv: list[str]) -> int:
     targets = set(argv) or {"runtime", "rt_py", "tests", "apps", "kernels", "ops_py", "eval_py", "optim_py",
                                   "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py", "ffm_py", "gbdt_py",
-                                  "lda_py"}
+                                  "lda_py", "sgns_py"}
     for kind in ("thread", "address"):
         if f"san_{kind}" in targets:
             for o in build_sanitized(kind):
@@ -327,7 +334,7 @@ def main(argv: list[str]) -> int:
         for o in build_apps(objs):
             print("built", o)
     if targets & {"kernels", "ops_py", "eval_py", "optim_py", "ftrl_py", "wideftrl_py", "fm_py", "deepfm_py", "dcn_py",
-                  "ffm_py", "gbdt_py", "lda_py"}:
+                  "ffm_py", "gbdt_py", "lda_py", "sgns_py"}:
         kobjs = kernel_objs()
         if targets & {"kernels", "ops_py"}:
             # always relink: a stale .so would silently run old kernels
@@ -352,6 +359,8 @@ def main(argv: list[str]) -> int:
             print("built", build_gbdt_py(kobjs))
         if targets & {"kernels", "lda_py"}:
             print("built", build_lda_py(kobjs))
+        if targets & {"kernels", "sgns_py"}:
+            print("built", build_sgns_py(kobjs))
     return 0
 
 
