@@ -28,6 +28,8 @@
   ``lda_loglik``): an eleventh small torch extension, same rule.
 * ``_w2vk``     -- the word2vec skip-gram negative-sampling kernels (``ops.sgns_lookups`` / ``sgns_forward`` /
   ``sgns_backward``): a twelfth small torch extension, same rule.
+* ``_alsk``     -- the ALS normal-equation kernels (``ops.als_solve`` / ``als_gram``): a thirteenth small torch
+  extension, same rule.
 """
 from __future__ import annotations
 
@@ -123,6 +125,11 @@ def w2vk():
     return _load("_w2vk", "gfx950 HIP word2vec skip-gram negative-sampling kernels")
 
 
+def alsk():
+    """Return the HIP ALS (alternating least squares) kernel module or raise a loud error."""
+    return _load("_alsk", "gfx950 HIP ALS normal-equation kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -174,6 +181,10 @@ def ldak_available() -> bool:
 
 def w2vk_available() -> bool:
     return _available(w2vk)
+
+
+def alsk_available() -> bool:
+    return _available(alsk)
 
 
 def native_dir() -> str:

@@ -370,3 +370,47 @@ class W2VSynth:
 
     def counts(self) -> torch.Tensor:
         return torch.bincount(self.tokens, minlength=self.vocab)
+
+
+class MFSynth:
+    """Low-rank ratings for matrix factorisation (models/als.py): teachers P [users, k_teacher] and Q [items,
+    k_teacher] ~ N(0, 1 / sqrt(k_teacher)); user u rates ``per_user`` distinct items (``zipf`` > 0 draws them from a
+    Zipf law of that exponent over the items instead of uniformly) with r = <P_u, Q_i> + noise N(0, 1). csr() returns
+    the matrix by user (rowptr int64 [users + 1], cols int64, vals fp32); holdout(seed) draws one more rating per user
+    the same way: (u, i, r). Generated on the host from ``seed`` alone."""
+
+    def __init__(self, users: int = 256, items: int = 128, k_teacher: int = 4, per_user: int = 24, noise: float = 0.1,
+                 seed: int = 0, zipf: float = 0.0):
+        if users < 1 or items < 1 or k_teacher < 1 or not 1 <= per_user <= items or noise < 0 or zipf < 0:
+            raise ValueError(f"MFSynth: users {users}, items {items}, k_teacher {k_teacher}, per_user {per_user}, "
+                             f"noise {noise}, zipf {zipf}")
+        self.users, self.items, self.per_user, self.noise, self.seed = users, items, per_user, noise, seed
+        gen = torch.Generator()
+        gen.manual_seed(seed + 1)
+        self.P = torch.randn(users, k_teacher, generator=gen) / k_teacher ** 0.25
+        self.Q = torch.randn(items, k_teacher, generator=gen) / k_teacher ** 0.25
+        w = torch.arange(1, items + 1, dtype=torch.float64).pow(-zipf) if zipf > 0 else torch.ones(items,
+                                                                                                  dtype=torch.float64)
+        self.weights = w
+        cols = torch.empty(users, per_user, dtype=torch.int64)
+        step = max(1, (1 << 22) // items)  # rows of multinomial without replacement, a block at a time
+        for lo in range(0, users, step):
+            hi = min(lo + step, users)
+            cols[lo:hi] = torch.multinomial(w.expand(hi - lo, items), per_user, generator=gen)
+        self.cols = torch.sort(cols, 1).values.reshape(-1)
+        self.rowptr = torch.arange(users + 1, dtype=torch.int64) * per_user
+        u = torch.arange(users).repeat_interleave(per_user)
+        self.vals = self._rate(u, self.cols, gen)
+
+    def _rate(self, u, i, gen):
+        return ((self.P[u] * self.Q[i]).sum(1) + self.noise * torch.randn(u.numel(), generator=gen)).float()
+
+    def csr(self):
+        return self.rowptr, self.cols, self.vals
+
+    def holdout(self, seed: int = 0):
+        gen = torch.Generator()
+        gen.manual_seed(self.seed + 7919 * (seed + 1))
+        u = torch.arange(self.users)
+        i = torch.multinomial(self.weights, self.users, replacement=True, generator=gen)
+        return u, i, self._rate(u, i, gen)

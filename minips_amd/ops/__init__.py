@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, ldak, optk, w2vk, wdftrlk
+from .._native import alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, ldak, optk, w2vk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1838,6 +1838,121 @@ def sgns_backward(inv, e, h, rows, N, grad_rows, csr=None, blocks=0):
     touched[inv[(inv >= 0) & (inv < cap)]] = True
     grad_rows[:cap][touched] = acc[touched]
     return grad_rows
+
+
+# ----------------------------------------------------------------------------- ALS: alternating least squares
+ALS_MIN_K, ALS_MAX_K, ALS_MAX_CHUNK = 4, 128, 1 << 20  # csrc/kernels/als.h (the binding exports them too)
+ALS_CHUNK = 4096
+_ALS_ROWS = 1 << 13  # lookups per pass of the CPU reference
+
+
+def _als_check(op, k, rows):
+    if k % 4 or not ALS_MIN_K <= k <= ALS_MAX_K:
+        raise RuntimeError(f"{op}: rows are {k} wide, expected k % 4 == 0 and {ALS_MIN_K} <= k <= {ALS_MAX_K}")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[1] < k:
+        raise RuntimeError(f"{op}: rows must be fp32 [cap, >= {k}], got {rows.dtype} {tuple(rows.shape)}")
+
+
+def als_chunks(rowptr_cpu, chunk: int = ALS_CHUNK):
+    """The chunk descriptors of a batch of entities (csrc/kernels/als.h), built on the host once: entity e with the
+    lookups [rowptr[e], rowptr[e + 1]) gets max(1, ceil(n_e / chunk)) descriptors (entity, lo, hi) of consecutive
+    lookup ranges. Returns (desc int32 [n_desc, 3], multi int32 [n_multi, 3], n_multi_desc): the descriptors of the
+    entities with more than one come first, in entity order, and ``multi`` lists those entities as (entity, first
+    descriptor, descriptors). CPU tensors; the caller moves them to the device."""
+    rp = rowptr_cpu.detach().to("cpu", torch.int64).reshape(-1)
+    chunk = int(chunk)
+    if rp.numel() < 1 or not 1 <= chunk <= ALS_MAX_CHUNK:
+        raise ValueError(f"als: als_chunks takes B + 1 row pointers and 1 <= chunk <= {ALS_MAX_CHUNK}, got "
+                         f"{rp.numel()} and {chunk}")
+    B = rp.numel() - 1
+    if B and (int(rp[0]) < 0 or bool((rp[1:] < rp[:-1]).any()) or int(rp[-1]) >= 1 << 31):
+        raise ValueError("als: rowptr must ascend from a value >= 0 and stay below 2^31")
+    ne = rp[1:] - rp[:-1]
+    nd = ((ne + chunk - 1) // chunk).clamp(min=1)
+    ids = torch.arange(B, dtype=torch.int64)
+    heavy = nd > 1
+    order = torch.cat([ids[heavy], ids[~heavy]])
+    cnt = nd[order]
+    ent = torch.repeat_interleave(order, cnt)
+    start = torch.cumsum(cnt, 0) - cnt
+    ci = torch.arange(ent.numel(), dtype=torch.int64) - torch.repeat_interleave(start, cnt)
+    lo = rp[ent] + ci * chunk
+    hi = torch.minimum(lo + chunk, rp[ent + 1])
+    desc = torch.stack([ent, lo, hi], 1).to(torch.int32).reshape(-1, 3)
+    nm = int(heavy.sum())
+    multi = torch.stack([order[:nm], start[:nm], cnt[:nm]], 1).to(torch.int32).reshape(-1, 3)
+    return desc, multi, int(cnt[:nm].sum())
+
+
+def als_solve(rowptr, inv, a, c, rows, reg, slot, x_old, x_out, delta, chunks, gram0=None, bad=None, blocks=0):
+    """One half-sweep's normal equations over pulled rows (the rule: csrc/kernels/als.h). Entity e has the lookups j
+    in [rowptr[e], rowptr[e + 1]); lookup j reads y_j = rows[inv[j]] (an inv outside [0, cap) contributes nothing)
+    with the weights a[j], c[j]. A_e = sum_j a_j y_j y_j^T + gram0 + reg[e] I, b_e = sum_j c_j y_j, x_e = A_e^-1 b_e by
+    Cholesky; x_out[slot[e]] = x_e and delta[slot[e]] = x_e - x_old[slot[e]]. An entity without a contributing
+    lookup, or whose factorisation meets a pivot <= 0 or not finite, keeps its old row with delta 0; the latter is
+    counted in ``bad`` (int32 [1]). ``chunks`` = als_chunks(rowptr) on rows' device. On the GPU one fused gfx950
+    launch (and a fold launch when an entity has several chunks): no atomics, the same bits on every run and for every
+    grid size (``blocks``); the CPU path is the fp32 PyTorch reference of the same rule (``chunks`` is not read)."""
+    k = x_out.shape[1] if x_out.dim() == 2 else 0
+    if _gpu(rows):
+        desc, multi, nmd = chunks
+        alsk().als_solve(rowptr, inv, a, c, rows, reg, slot, x_old, x_out, delta, desc, multi, int(nmd), gram0, bad,
+                         int(blocks))
+        return x_out, delta
+    _als_check("als_solve", k, rows)
+    B, n, cap, m = rowptr.numel() - 1, inv.numel(), rows.shape[0], x_out.shape[0]
+    if a.numel() != n or c.numel() != n or reg.numel() != B or slot.numel() != B or x_old.shape != x_out.shape or \
+            delta.shape != x_out.shape or (gram0 is not None and tuple(gram0.shape) != (k, k)):
+        raise RuntimeError(f"als_solve: {B} entities, inv [{n}], a [{a.numel()}], c [{c.numel()}], reg [{reg.numel()}],"
+                           f" slot [{slot.numel()}], x_old {tuple(x_old.shape)}, x_out {tuple(x_out.shape)}, delta "
+                           f"{tuple(delta.shape)}")
+    if B == 0:
+        return x_out, delta
+    rp = torch.cummax(rowptr.clamp(0, n), 0).values
+    A = torch.zeros(B, k, k, dtype=torch.float32)
+    b = torch.zeros(B, k, dtype=torch.float32)
+    cnt = torch.zeros(B, dtype=torch.int64)
+    for lo in range(0, n, _ALS_ROWS):
+        j = torch.arange(lo, min(lo + _ALS_ROWS, n), dtype=torch.int64)
+        e = torch.searchsorted(rp, j, right=True) - 1
+        iv = inv[j]
+        ok = (e >= 0) & (e < B) & (iv >= 0) & (iv < cap)
+        j, e, iv = j[ok], e[ok], iv[ok]
+        Y = rows[iv][:, :k]
+        A.index_add_(0, e, (a[j, None] * Y)[:, :, None] * Y[:, None, :])
+        b.index_add_(0, e, c[j, None] * Y)
+        cnt.index_add_(0, e, torch.ones_like(e))
+    if gram0 is not None:
+        A += gram0
+    A += reg[:, None, None] * torch.eye(k, dtype=torch.float32)
+    Lc, info = torch.linalg.cholesky_ex(A)
+    failed = (info != 0) | ~torch.isfinite(Lc).all(-1).all(-1)
+    Lc = torch.where(failed[:, None, None], torch.eye(k, dtype=torch.float32), Lc)
+    x = torch.cholesky_solve(b[:, :, None], Lc)[:, :, 0]
+    solved = (cnt > 0) & ~failed
+    inside = (slot >= 0) & (slot < m)
+    sl = slot[inside]
+    old = x_old[sl]
+    new = torch.where(solved[inside][:, None], x[inside], old)
+    x_out[sl] = new
+    delta[sl] = torch.where(solved[inside][:, None], new - old, torch.zeros_like(old))
+    if bad is not None:
+        bad += int(((cnt > 0) & failed).sum())
+    return x_out, delta
+
+
+def als_gram(rows, k=None):
+    """G fp32 [k, k] = rows[:, :k]^T rows[:, :k] (ALS's shared Y^T Y of implicit feedback). On the GPU strips of
+    shard rows are multiplied by fp32 MFMA, a workgroup each, and folded in index order (the same bits on every run);
+    the CPU path is the fp32 matrix product."""
+    k = int(rows.shape[1] if k is None else k)
+    if _gpu(rows):
+        out = torch.empty(k, k, dtype=torch.float32, device=rows.device)
+        alsk().als_gram(rows, out)
+        return out
+    _als_check("als_gram", k, rows)
+    Y = rows[:, :k]
+    return Y.t() @ Y
 
 
 # ----------------------------------------------------------------------------- optimizers

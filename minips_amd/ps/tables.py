@@ -1380,6 +1380,15 @@ class SparseTable:
         self.shard[mine] = 0
         return self
 
+    def local_rows(self, lo: int, hi: int) -> torch.Tensor:
+        """The rows of the keys [lo, hi) that this rank holds, as a view of its shard (possibly empty), behind the
+        same read gate as a Get. Range-routed tables only: there a key range is a row range."""
+        if self.route_mult:
+            raise ValueError("local_rows reads a key range of a range-routed table (route='range')")
+        self.pipe.wait_for_read()
+        a, b = max(lo, self.base), min(hi, self.base + self.rows_local)
+        return self.shard[a - self.base: max(b, a) - self.base]
+
     def get_rows(self, keys: torch.Tensor) -> torch.Tensor:
         """Reference-style Get: the values of every requested key, in request order."""
         rows, plan = self.get(keys)

@@ -29,6 +29,12 @@ resident corpus -- --w2v_sentences synthetic sentences of --w2v_len tokens over 
 libsvm file whose lines are sentences in file order (`label word:x ...`, ids minus one, values ignored);
 --w2v_dim / --w2v_negatives / --w2v_window / --w2v_sample / --w2v_vocab, --batch pairs per clock; the reported loss
 is the epoch's mean pair loss; the final JSON gains w2v_dim, w2v_pairs and (synthetic) w2v_purity, collective only.
+--model als is collaborative filtering by alternating least squares (models/als.py): --steps counts sweeps (the
+user half, then the item half) over a resident rating matrix -- --als_users x --als_items synthetic low-rank ratings,
+--als_per_user a user (MFSynth), every rank an even slice of each side, or on one rank an --input libsvm file whose
+lines are users (`label item:rating ...`); --als_k / --als_reg / --als_implicit / --als_alpha, --batch entities
+per clock; the reported loss is the held-out (synthetic) or training RMSE; the final JSON gains als_k and als_rmse,
+collective BSP only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -54,7 +60,7 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v"])
+                                                             "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v", "als"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -193,6 +199,18 @@ def parse(argv=None):
                     help="w2v, synthetic data: sentences over all ranks (default 512 with --small, else 262144)")
     ap.add_argument("--w2v_len", type=int, default=None,
                     help="w2v, synthetic data: tokens per sentence (default 16 with --small, else 32)")
+    ap.add_argument("--als_k", type=int, default=None, help="als: factors, a multiple of 4 in [4, 128] (default 8 with "
+                                                            "--small, else 32)")
+    ap.add_argument("--als_reg", type=float, default=None, help="als: lambda > 0 (default 0.05)")
+    ap.add_argument("--als_implicit", action="store_true", default=None,
+                    help="als: implicit feedback (Hu, Koren and Volinsky) instead of explicit ALS-WR")
+    ap.add_argument("--als_alpha", type=float, default=None, help="als, implicit: the confidence slope (default 40)")
+    ap.add_argument("--als_users", type=int, default=None,
+                    help="als: users (synthetic default: 256 with --small, else 131072; with --input: the lines)")
+    ap.add_argument("--als_items", type=int, default=None,
+                    help="als: items (synthetic default: 128 with --small, else 32768; with --input: the largest id)")
+    ap.add_argument("--als_per_user", type=int, default=None,
+                    help="als, synthetic data: ratings per user (default 24 with --small, else 64)")
     args = ap.parse_args(argv)
     if args.sparse_optimizer == "ftrl":
         if args.model != "lr":
@@ -350,6 +368,42 @@ def parse(argv=None):
                      "mean pair loss)")
     elif w2v_flags:
         ap.error(f"{' / '.join(w2v_flags)}: --model w2v only, not {args.model}")
+    als_flags = [f"--{k}" for k in ("als_k", "als_reg", "als_implicit", "als_alpha", "als_users", "als_items",
+                                    "als_per_user") if getattr(args, k) is not None]
+    if args.model == "als":
+        args.als_k = (8 if args.small else 32) if args.als_k is None else args.als_k
+        args.als_reg = 0.05 if args.als_reg is None else args.als_reg
+        args.als_implicit = bool(args.als_implicit)
+        args.als_alpha = 40.0 if args.als_alpha is None else args.als_alpha
+        if args.als_k % 4 or not 4 <= args.als_k <= 128:
+            ap.error(f"--model als: --als_k {args.als_k} must be a multiple of 4 in [4, 128]")
+        if not args.als_reg > 0:
+            ap.error(f"--model als: --als_reg {args.als_reg} must be > 0")
+        if not args.als_alpha > 0:
+            ap.error(f"--model als: --als_alpha {args.als_alpha} must be > 0")
+        if args.input and args.als_per_user is not None:
+            ap.error("--model als: --als_per_user sizes the synthetic ratings, not an --input file")
+        if not args.input:
+            args.als_users = (256 if args.small else 131072) if args.als_users is None else args.als_users
+            args.als_items = (128 if args.small else 32768) if args.als_items is None else args.als_items
+            args.als_per_user = (24 if args.small else 64) if args.als_per_user is None else args.als_per_user
+            if args.als_users < 1 or args.als_items < 1 or not 1 <= args.als_per_user <= args.als_items:
+                ap.error("--model als: --als_users and --als_items must be >= 1 and 1 <= --als_per_user <= --als_items")
+        if args.batch < 0:
+            ap.error(f"--model als: --batch {args.batch} entities per clock must be >= 1 (0: 4096)")
+        if args.transport == "onesided":
+            ap.error("--model als needs --transport collective (no als on the one-sided transport)")
+        if args.consistency != "bsp":
+            ap.error(f"--model als needs --consistency bsp, not {args.consistency} (a half-sweep reads one side while "
+                     f"it writes the other)")
+        if args.kStorageType != "vector":
+            ap.error("--model als needs --kStorageType Vector (no als on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model als keeps float32 rows, not --value_dtype {args.value_dtype}")
+        if args.eval_every > 0:
+            ap.error("--model als: no --eval_every (every sweep reports the held-out RMSE)")
+    elif als_flags:
+        ap.error(f"{' / '.join(als_flags)}: --model als only, not {args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -740,6 +794,46 @@ def build(args, comm):
 
         # epoch() returns the epoch's mean pair loss over all ranks (collective, read on the host once an epoch)
         return m, {0: m.table}, (lambda: _Epochs(None)), (lambda _: torch.tensor([m.epoch()], device=dev)), 1
+    if args.model == "als":
+        from .models.als import ALS, ALSConfig, transpose_csr
+        from .ps.tables import even_bounds
+
+        if args.input:  # every line a user: `label item:rating ...` (ids minus one); one rank holds the whole matrix
+            if comm.world > 1:
+                raise ValueError("als: an --input file is read on one rank (the item half needs the whole transpose); "
+                                 "use the synthetic ratings on several ranks")
+            shard = args._shard
+            rp, cols, vals = shard.rowptr.long().cpu(), shard.cols.long().cpu(), shard.vals.float().cpu()
+            U = args.als_users if args.als_users is not None else rp.numel() - 1
+            I = args.als_items if args.als_items is not None else (int(cols.max()) + 1 if cols.numel() else 1)
+            hold = None
+        else:
+            from .data.synthetic import MFSynth
+
+            U, I = args.als_users, args.als_items
+            synth = MFSynth(U, I, k_teacher=4, per_user=args.als_per_user, noise=0.1, seed=args.seed)
+            rp, cols, vals = synth.csr()
+            if args.als_implicit:
+                vals = vals.abs()
+            hold = synth.holdout(0)
+        m = ALS(ALSConfig(users=U, items=I, k=args.als_k, reg=args.als_reg, implicit=args.als_implicit,
+                          alpha=args.als_alpha, batch_entities=args.batch or 4096, seed=args.seed), comm)
+        tp, trows, tvals = transpose_csr(rp, cols, vals, I)
+        for attach, p, c, v, n in ((m.attach_users, rp, cols, vals, U), (m.attach_items, tp, trows, tvals, I)):
+            b = even_bounds(n, comm.world)
+            lo, hi = b[comm.rank], b[comm.rank + 1]
+            attach(p[lo:hi + 1] - p[lo], c[int(p[lo]):int(p[hi])], v[int(p[lo]):int(p[hi])], lo)
+        if hold is None:  # the training ratings of this rank's users
+            su = m.sides["users"]
+            uid = torch.repeat_interleave(torch.arange(su["E"], device=dev), su["rowptr"][1:] - su["rowptr"][:-1])
+            hold = (uid + su["base"], su["cols"], su["vals"])
+        args._als_hold = hold
+
+        def als_step(_):  # a sweep; its RMSE is a collective read on the host once a sweep
+            m.sweep()
+            return torch.tensor([m.rmse(*hold)], device=dev)
+
+        return m, {0: m.table}, (lambda: _Resident(None)), als_step, 1
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
         # shard stays resident in HBM and batches are consecutive rows, cut on the device
@@ -961,7 +1055,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda", "w2v") and args.input:
+    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda", "w2v", "als") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -1203,6 +1297,8 @@ def main(argv=None):
     if args.model == "lda":  # the topic totals are replicated: their sum is the corpus's token count
         sums = model.nk.double().sum().reshape(1)
         ftrl_final.update(lda_topics=model.K, lda_tokens=int(model.nk.sum()), lda_loglik=round(model.loglik(), 6))
+    if args.model == "als":  # rmse() is a collective Get
+        ftrl_final.update(als_k=model.k, als_rmse=round(model.rmse(*args._als_hold), 6))
     if args.model == "w2v":  # vectors() is a collective Get; the purity of the planted groups is read on the host
         ftrl_final.update(w2v_dim=model.d, w2v_pairs=model.total_pairs)
         if args._w2v_group:

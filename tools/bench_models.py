@@ -15,7 +15,9 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         gbdt (a boosting round of the fixed-point histogram GBDT over --batch resident samples per rank; --gbdt_depth,
         --gbdt_bins, --gbdt_features; ms_per_step is ms per tree), lda (a sweep of the fixed-point collapsed Gibbs
         sampler over --batch resident tokens per rank; --lda_topics; ms_per_step is ms per sweep), w2v (a clock of
-        word2vec skip-gram with negative sampling on --batch pairs of Zipf words; --w2v_dim, --w2v_negatives).
+        word2vec skip-gram with negative sampling on --batch pairs of Zipf words; --w2v_dim, --w2v_negatives), als
+        (a sweep of alternating least squares over 131072 users x 32768 Zipf items per rank, 64 ratings a user,
+        clocks of --batch entities; --als_k; ms_per_step is ms per sweep).
 """
 from __future__ import annotations
 
@@ -212,6 +214,24 @@ def build(args, comm):
         return m, step, B, "pairs/s", \
             dict(model=f"word2vec skip-gram, {args.w2v_negatives} negatives, {V} words, fp32 rows of {args.w2v_dim}, "
                        f"Zipf(1.05) words", seq_len=None)
+    if args.model == "als":
+        from minips_amd.data.synthetic import MFSynth
+        from minips_amd.models.als import ALS, ALSConfig, transpose_csr
+
+        # a sweep (user half, item half) over this rank's slice of 131072 x world users and 32768 x world items, 64
+        # ratings a user on Zipf(1.05) items: the popular items take the multi-chunk path
+        Ul, Il = 131072, 32768
+        synth = MFSynth(Ul * comm.world, Il * comm.world, k_teacher=8, per_user=64, noise=0.1, seed=3, zipf=1.05)
+        rp, cols, vals = synth.csr()
+        tp, trows, tvals = transpose_csr(rp, cols, vals, synth.items)
+        m = ALS(ALSConfig(users=synth.users, items=synth.items, k=args.als_k, batch_entities=args.batch or 4096,
+                          consistency=args.consistency, staleness=args.staleness), comm)
+        for attach, p, c, v, n in ((m.attach_users, rp, cols, vals, Ul), (m.attach_items, tp, trows, tvals, Il)):
+            lo, hi = r * n, (r + 1) * n
+            attach(p[lo:hi + 1] - p[lo], c[int(p[lo]):int(p[hi])], v[int(p[lo]):int(p[hi])], lo)
+        return m, m.sweep, Ul * 64, "ratings/s", \
+            dict(model=f"ALS-WR, k {args.als_k}, {synth.users} users x {synth.items} Zipf(1.05) items, 64 ratings a "
+                       f"user, clocks of {args.batch or 4096} entities, fp32 rows", seq_len=None)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -290,7 +310,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
                                                          "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
-                                                         "gbdt", "lda", "w2v"])
+                                                         "gbdt", "lda", "w2v", "als"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -334,6 +354,7 @@ def main():
     ap.add_argument("--w2v_dim", "--w2v-dim", dest="w2v_dim", type=int, default=128, help="w2v: vector width")
     ap.add_argument("--w2v_negatives", "--w2v-negatives", dest="w2v_negatives", type=int, default=5,
                     help="w2v: negatives per pair")
+    ap.add_argument("--als_k", "--als-k", dest="als_k", type=int, default=32, help="als: factors")
     ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
                     help="gbdt: features (the teacher reads 5)")
     args = ap.parse_args()
