@@ -30,6 +30,8 @@
   ``sgns_backward``): a twelfth small torch extension, same rule.
 * ``_alsk``     -- the ALS normal-equation kernels (``ops.als_solve`` / ``als_gram``): a thirteenth small torch
   extension, same rule.
+* ``_gmmk``     -- the Gaussian-mixture EM-step kernels (``ops.gmm_prepare`` / ``gmm_estep``): a fourteenth small
+  torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -130,6 +132,11 @@ def alsk():
     return _load("_alsk", "gfx950 HIP ALS normal-equation kernels")
 
 
+def gmmk():
+    """Return the HIP Gaussian-mixture EM-step kernel module or raise a loud error."""
+    return _load("_gmmk", "gfx950 HIP Gaussian-mixture EM-step kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -185,6 +192,10 @@ def w2vk_available() -> bool:
 
 def alsk_available() -> bool:
     return _available(alsk)
+
+
+def gmmk_available() -> bool:
+    return _available(gmmk)
 
 
 def native_dir() -> str:

@@ -414,3 +414,43 @@ class MFSynth:
         u = torch.arange(self.users)
         i = torch.multinomial(self.weights, self.users, replacement=True, generator=gen)
         return u, i, self._rate(u, i, gen)
+
+
+class GMMSynth:
+    """Points from a planted diagonal Gaussian mixture (models/gmm.py): ``K_teacher`` components with centres ~
+    ``sep`` N(0, 1) around a common offset, per-dimension standard deviations uniform in [0.5, 2] and weights
+    proportional to U(0.5, 1.5), all drawn from ``seed`` alone (one teacher for every rank). next() returns X fp32
+    [batch, dims]; ``labels`` holds the planted component of the last batch; holdout(seed) is an independent sample
+    stream of the same teacher; loglik(X) is the teacher's own mean log density in fp64."""
+
+    def __init__(self, batch: int, dims: int = 8, K_teacher: int = 4, sep: float = 4.0, seed: int = 0, device="cpu"):
+        if batch < 1 or dims < 1 or K_teacher < 1 or sep < 0:
+            raise ValueError(f"GMMSynth: batch {batch}, dims {dims}, K_teacher {K_teacher}, sep {sep}")
+        self.batch, self.dims, self.K = batch, dims, K_teacher
+        self.device = torch.device(device)
+        g = torch.Generator().manual_seed(seed + 1)
+        self.offset = torch.randn(dims, generator=g) * 3.0
+        self.centres = (self.offset + sep * torch.randn(K_teacher, dims, generator=g)).to(self.device)
+        self.sigma = (0.5 + 1.5 * torch.rand(K_teacher, dims, generator=g)).to(self.device)
+        w = 0.5 + torch.rand(K_teacher, generator=g)
+        self.weights = (w / w.sum()).to(self.device)
+        self.gen = torch.Generator(device=self.device).manual_seed(seed + 2)
+        self.labels = None
+
+    def holdout(self, seed: int) -> "GMMSynth":
+        h = GMMSynth.__new__(GMMSynth)
+        h.__dict__.update(self.__dict__)
+        h.gen = torch.Generator(device=self.device).manual_seed(seed)
+        return h
+
+    def next(self):
+        z = torch.multinomial(self.weights, self.batch, replacement=True, generator=self.gen)
+        self.labels = z
+        eps = torch.randn(self.batch, self.dims, generator=self.gen, device=self.device)
+        return (self.centres[z] + self.sigma[z] * eps).float()
+
+    def loglik(self, X: torch.Tensor) -> float:
+        x, mu, sd = X.double()[:, None, :], self.centres.double().to(X.device), self.sigma.double().to(X.device)
+        t = torch.log(self.weights.double().to(X.device)) - (0.5 * ((x - mu) / sd) ** 2 + torch.log(sd)).sum(2) \
+            - 0.5 * self.dims * 1.8378770664093453
+        return float(torch.logsumexp(t, 1).mean())

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, kernels, ldak, optk, w2vk, wdftrlk
+from .._native import alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmk, kernels, ldak, optk, w2vk, wdftrlk
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1953,6 +1953,101 @@ def als_gram(rows, k=None):
     _als_check("als_gram", k, rows)
     Y = rows[:, :k]
     return Y.t() @ Y
+
+
+# ----------------------------------------------------------------------------- GMM: Gaussian mixture by EM
+GMM_MAX_K, GMM_MAX_D, GMM_MAX_KD, GMM_CHUNK = 128, 128, 8192, 2048  # csrc/kernels/gmm.h (the binding exports them too)
+_GMM_LOG_2PI = 1.8378770664093453
+
+
+def gmm_pad(v: int) -> int:
+    return (int(v) + 15) // 16 * 16
+
+
+def gmm_shape_ok(K: int, D: int) -> bool:
+    return 1 <= K <= GMM_MAX_K and 1 <= D <= GMM_MAX_D and gmm_pad(K) * gmm_pad(D) <= GMM_MAX_KD
+
+
+def _gmm_check(op, K, D):
+    if not gmm_shape_ok(K, D):
+        raise ValueError(f"gmm: {op}: K = {K}, D = {D}, expected 1 <= K <= {GMM_MAX_K}, 1 <= D <= {GMM_MAX_D} and "
+                         f"KP * DP = {gmm_pad(K) * gmm_pad(D)} <= {GMM_MAX_KD}")
+
+
+def gmm_prepare(s, var_floor: float = 1e-4):
+    """The E-step's operands from the normalised sufficient statistics s fp32 [K, 2D + 1] (the rule: csrc/kernels/
+    gmm.h): coef fp32 [K, 2 DP] (-0.5 / var | mu / var, pad columns 0) and cst fp32 [K] (log pi - 0.5 sum (mu^2 / var +
+    log var) - D / 2 log 2 pi). A component with s0 <= 0, a non-finite statistic or a non-finite cst is dead: cst =
+    -inf, its coef row 0. On the GPU one gfx950 launch, a wave per component; the CPU path is the fp32 PyTorch
+    reference of the same rule."""
+    if s.dim() != 2 or s.shape[1] % 2 != 1 or s.dtype != torch.float32:
+        raise ValueError(f"gmm: gmm_prepare takes s fp32 [K, 2D + 1], got {s.dtype} {tuple(s.shape)}")
+    K, D = s.shape[0], (s.shape[1] - 1) // 2
+    _gmm_check("gmm_prepare", K, D)
+    if not (var_floor > 0 and var_floor < float("inf")):
+        raise ValueError(f"gmm: var_floor is {var_floor}, expected a finite value > 0")
+    dp = gmm_pad(D)
+    if _gpu(s):
+        coef = torch.empty(K, 2 * dp, dtype=torch.float32, device=s.device)
+        cst = torch.empty(K, dtype=torch.float32, device=s.device)
+        gmmk().gmm_prepare(s.contiguous(), float(var_floor), coef, cst)
+        return coef, cst
+    s0, s1, s2 = s[:, 2 * D], s[:, :D], s[:, D:2 * D]
+    live0 = torch.isfinite(s0) & (s0 > 0)
+    tot = torch.where(live0, s0, torch.zeros(())).sum()
+    mu = s1 / s0[:, None]
+    v = s2 / s0[:, None] - mu * mu
+    var = torch.where(v > var_floor, v, torch.full((), float(var_floor)))
+    cst = torch.log(s0 / tot) - 0.5 * (mu * mu / var + torch.log(var)).sum(1) - 0.5 * D * _GMM_LOG_2PI
+    dead = ~live0 | ~torch.isfinite(s[:, :2 * D]).all(1) | ~torch.isfinite(cst)
+    coef = torch.zeros(K, 2 * dp, dtype=torch.float32)
+    coef[:, :D] = torch.where(dead[:, None], torch.zeros(()), -0.5 / var)
+    coef[:, dp:dp + D] = torch.where(dead[:, None], torch.zeros(()), mu / var)
+    return coef, torch.where(dead, torch.full((), float("-inf")), cst)
+
+
+def gmm_estep(X, shift, coef, cst, accumulate=True, want_assign=False, want_logp=False, bad=None, blocks=0):
+    """The E-step of a diagonal Gaussian mixture over the points X fp32 [n, D] (row stride >= D; the rule:
+    csrc/kernels/gmm.h), x = X - shift: t_ik = cst_k + sum_d (coef[k, d] x_d^2 + coef[k, DP + d] x_d), lse_i =
+    logsumexp_k t_ik, r_ik = exp(t_ik - lse_i). Returns (S, ll, assign, logp): S fp32 [K, 2D + 1] = the sums over i of
+    r x | r x^2 | r (None with accumulate=False, the predict path), ll fp64 [1] = sum_i lse_i, assign int32 [n] the
+    argmax (lowest index on ties) and logp fp32 [n] = lse_i when asked for. A point whose lse is not finite contributes
+    nothing, is counted in ``bad`` (int32 [1]) and gets assign -1, logp NaN. On the GPU one fused gfx950 launch and a
+    fold launch: scores and statistics by fp32 MFMA, the responsibilities never leave the workgroup, no float atomics,
+    the same bits on every run and for every grid size (``blocks``); the CPU path is the fp32 PyTorch reference."""
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError(f"gmm: gmm_estep takes fp32 points [n, D], got {X.dtype} {tuple(X.shape)}")
+    n, D, K = X.shape[0], shift.numel(), cst.numel()
+    _gmm_check("gmm_estep", K, D)
+    dp = gmm_pad(D)
+    if X.shape[1] != D or tuple(coef.shape) != (K, 2 * dp):
+        raise ValueError(f"gmm: gmm_estep: X {tuple(X.shape)}, shift [{D}], coef {tuple(coef.shape)}, cst [{K}]: "
+                         f"expected X [n, {D}] and coef [{K}, {2 * dp}]")
+    dev = X.device
+    if _gpu(X):
+        S = torch.empty(K, 2 * D + 1, dtype=torch.float32, device=dev) if accumulate else None
+        ll = torch.empty(1, dtype=torch.float64, device=dev)
+        assign = torch.empty(n, dtype=torch.int32, device=dev) if want_assign else None
+        logp = torch.empty(n, dtype=torch.float32, device=dev) if want_logp else None
+        gmmk().gmm_estep(X, shift, coef, cst, S, ll, assign, logp, bad, int(blocks))
+        return S, ll, assign, logp
+    x = X - shift
+    t = cst + (x * x) @ coef[:, :D].t() + x @ coef[:, dp:dp + D].t()
+    m = torch.where(torch.isnan(t), torch.full((), float("-inf")), t).max(1).values
+    lse = m + torch.log(torch.exp(t - m[:, None]).sum(1))
+    ok = torch.isfinite(lse)
+    r = torch.where(ok[:, None], torch.exp(t - lse[:, None]), torch.zeros(()))
+    x = torch.where(ok[:, None], x, torch.zeros(()))
+    S = torch.cat([r.t() @ x, r.t() @ (x * x), r.sum(0)[:, None]], 1) if accumulate else None
+    ll = torch.where(ok, lse, torch.zeros(())).double().sum().reshape(1)
+    if bad is not None:
+        bad += int((~ok).sum())
+    assign = None
+    if want_assign:  # the lowest index among the maxima
+        first = torch.where(t == m[:, None], torch.arange(K), torch.full((), K)).min(1).values
+        assign = torch.where(ok, first, torch.full((), -1)).to(torch.int32)
+    logp = torch.where(ok, lse, torch.full((), float("nan"))) if want_logp else None
+    return S, ll, assign, logp
 
 
 # ----------------------------------------------------------------------------- optimizers

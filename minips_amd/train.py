@@ -35,6 +35,10 @@ user half, then the item half) over a resident rating matrix -- --als_users x --
 lines are users (`label item:rating ...`); --als_k / --als_reg / --als_implicit / --als_alpha, --batch entities
 per clock; the reported loss is the held-out (synthetic) or training RMSE; the final JSON gains als_k and als_rmse,
 collective BSP only.
+--model gmm is a diagonal Gaussian mixture fitted by stepwise EM (models/gmm.py): --K components over --num_dims
+dimensions, points from a planted mixture (GMMSynth) or an --input libsvm file densified a batch at a time (refused
+above 128 features); --gmm_rho0 / --gmm_kappa / --gmm_var_floor, --kmeans_init_mode seeds the centres; the reported
+loss is the batch's mean log-likelihood; the final JSON gains gmm_K and gmm_loglik, collective only.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -60,7 +64,8 @@ def _flag_bool(v):
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
-                                                             "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v", "als"])
+                                                             "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v", "als",
+                                                             "gmm"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -199,6 +204,11 @@ def parse(argv=None):
                     help="w2v, synthetic data: sentences over all ranks (default 512 with --small, else 262144)")
     ap.add_argument("--w2v_len", type=int, default=None,
                     help="w2v, synthetic data: tokens per sentence (default 16 with --small, else 32)")
+    ap.add_argument("--gmm_rho0", type=float, default=None,
+                    help="gmm: the stepwise-EM step rho_t = rho0 (t + 1)^-kappa, 0 < rho0 <= 1 (default 1)")
+    ap.add_argument("--gmm_kappa", type=float, default=None,
+                    help="gmm: the step's decay exponent in [0, 1] (default 0.6)")
+    ap.add_argument("--gmm_var_floor", type=float, default=None, help="gmm: the variance floor > 0 (default 1e-4)")
     ap.add_argument("--als_k", type=int, default=None, help="als: factors, a multiple of 4 in [4, 128] (default 8 with "
                                                             "--small, else 32)")
     ap.add_argument("--als_reg", type=float, default=None, help="als: lambda > 0 (default 0.05)")
@@ -404,6 +414,38 @@ def parse(argv=None):
             ap.error("--model als: no --eval_every (every sweep reports the held-out RMSE)")
     elif als_flags:
         ap.error(f"{' / '.join(als_flags)}: --model als only, not {args.model}")
+    gmm_flags = [f"--{k}" for k in ("gmm_rho0", "gmm_kappa", "gmm_var_floor") if getattr(args, k) is not None]
+    if args.model == "gmm":
+        from .ops import GMM_MAX_D, gmm_shape_ok
+
+        args.gmm_rho0 = 1.0 if args.gmm_rho0 is None else args.gmm_rho0
+        args.gmm_kappa = 0.6 if args.gmm_kappa is None else args.gmm_kappa  # a stream of batches: a decaying step
+        args.gmm_var_floor = 1e-4 if args.gmm_var_floor is None else args.gmm_var_floor
+        args.K = args.K or (4 if args.small else 64)
+        if not args.input:
+            args.num_dims = args.num_dims or (8 if args.small else 64)
+        if args.num_dims and not gmm_shape_ok(args.K, args.num_dims):
+            ap.error(f"--model gmm: --K {args.K} and --num_dims {args.num_dims} must lie in [1, 128] with "
+                     f"16 ceil(K / 16) * 16 ceil(D / 16) <= 8192")
+        if not 1 <= args.K <= 128 or args.num_dims > GMM_MAX_D:
+            ap.error(f"--model gmm: --K {args.K} must lie in [1, 128] and --num_dims {args.num_dims} in [1, 128] (an "
+                     f"--input file is densified)")
+        if not 0 < args.gmm_rho0 <= 1 or not 0 <= args.gmm_kappa <= 1:
+            ap.error("--model gmm: --gmm_rho0 must lie in (0, 1] and --gmm_kappa in [0, 1]")
+        if not 0 < args.gmm_var_floor < float("inf"):
+            ap.error(f"--model gmm: --gmm_var_floor {args.gmm_var_floor} must be a finite value > 0")
+        if args.batch < 0:
+            ap.error(f"--model gmm: --batch {args.batch} points per clock must be >= 1 (0: the default)")
+        if args.transport == "onesided":
+            ap.error("--model gmm needs --transport collective (no gmm on the one-sided transport)")
+        if args.kStorageType != "vector":
+            ap.error("--model gmm needs --kStorageType Vector (the statistics are one dense table)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model gmm keeps float32 statistics, not --value_dtype {args.value_dtype}")
+        if args.eval_every > 0:
+            ap.error("--model gmm: no --eval_every (the final JSON reports the held-out log-likelihood)")
+    elif gmm_flags:
+        ap.error(f"{' / '.join(gmm_flags)}: --model gmm only, not {args.model}")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -834,6 +876,45 @@ def build(args, comm):
             return torch.tensor([m.rmse(*hold)], device=dev)
 
         return m, {0: m.table}, (lambda: _Resident(None)), als_step, 1
+    if args.model == "gmm":
+        from .models.gmm import GMM, GMMConfig
+
+        def gmm_cfg(D):
+            return GMMConfig(K=args.K, dims=D, var_floor=args.gmm_var_floor, rho0=args.gmm_rho0, kappa=args.gmm_kappa,
+                             consistency=args.consistency, staleness=args.staleness, seed=seed,
+                             init_mode=args.kmeans_init_mode or "kmeans++")
+
+        if args.input:  # every libsvm batch is densified with torch: an absent feature is 0.0
+            shard = args._shard.to(dev)
+            nd = args.num_dims
+            if not nd:  # every rank must size the table alike: max feature id over all shards
+                t = torch.tensor([float(shard.cols.max()) + 1 if shard.cols.numel() else 1.0], device=dev)
+                comm.all_reduce_(t, op=dist.ReduceOp.MAX)
+                nd = int(t.item())
+            if nd > 128:
+                raise ValueError(f"gmm: the input holds {nd} features; a densified --input is refused above D = 128")
+            B = args.batch or 256
+
+            def dense(b):
+                rp, c, v = b[0], b[1], b[2]
+                X = torch.zeros(rp.numel() - 1, nd, dtype=torch.float32, device=dev)
+                row = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=dev), rp[1:] - rp[:-1])
+                ok = (c >= 0) & (c < nd)
+                return X.index_put_((row[ok], c[ok].long()), v[ok].float(), accumulate=True)
+
+            init = dense(shard.batch(0, max(B, args.K)))
+            m = GMM(gmm_cfg(nd), comm, init_data=init)
+            args._gmm_hold = init
+            return m, {0: m.table}, (lambda: _Skippable(_Batches(shard, B, seed))), \
+                (lambda b: m.train_step(dense(b))), B
+        from .data.synthetic import GMMSynth
+
+        B = args.batch or (256 if args.small else 65536)
+        # one teacher for every rank (seed), this rank's own sample stream; seeding reads its own batch
+        synth = GMMSynth(B, dims=args.num_dims, K_teacher=args.K, sep=4.0, seed=args.seed, device=dev)
+        m = GMM(gmm_cfg(args.num_dims), comm, init_data=synth.holdout(seed + 7919).next())
+        args._gmm_hold = synth.holdout(args.seed + 104729).next()  # the same held-out points on every rank
+        return m, {0: m.table}, (lambda: _Skippable(synth.holdout(seed + 1))), (lambda b: m.train_step(b)), B
     if args.model == "kmeans" and args.input:
         # the reference K-Means input: sparse libsvm points (kmeans.cpp reads --input); the
         # shard stays resident in HBM and batches are consecutive rows, cut on the device
@@ -1055,7 +1136,7 @@ def main(argv=None):
         # rank can roll back in its process (the one-sided tables cannot: peers hold IPC mappings of
         # the dead rank's shards and a shared progress board -- the whole set restarts instead)
         hb.write_caps(inplace=inplace, transport=args.transport)
-    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda", "w2v", "als") and args.input:
+    if args.model in ("lr", "kmeans", "fm", "ffm", "gbdt", "lda", "w2v", "als", "gmm") and args.input:
         from .data.loader import LibsvmData
 
         args._shard = _load_input(args, comm)
@@ -1299,6 +1380,9 @@ def main(argv=None):
         ftrl_final.update(lda_topics=model.K, lda_tokens=int(model.nk.sum()), lda_loglik=round(model.loglik(), 6))
     if args.model == "als":  # rmse() is a collective Get
         ftrl_final.update(als_k=model.k, als_rmse=round(model.rmse(*args._als_hold), 6))
+    if args.model == "gmm":  # the mean log density of the held-out points (the seeding batch with --input)
+        ftrl_final.update(gmm_K=model.cfg.K,
+                          gmm_loglik=round(float(model.predict(args._gmm_hold)[1].double().mean()), 6))
     if args.model == "w2v":  # vectors() is a collective Get; the purity of the planted groups is read on the host
         ftrl_final.update(w2v_dim=model.d, w2v_pairs=model.total_pairs)
         if args._w2v_group:

@@ -17,7 +17,8 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         sampler over --batch resident tokens per rank; --lda_topics; ms_per_step is ms per sweep), w2v (a clock of
         word2vec skip-gram with negative sampling on --batch pairs of Zipf words; --w2v_dim, --w2v_negatives), als
         (a sweep of alternating least squares over 131072 users x 32768 Zipf items per rank, 64 ratings a user,
-        clocks of --batch entities; --als_k; ms_per_step is ms per sweep).
+        clocks of --batch entities; --als_k; ms_per_step is ms per sweep), gmm (a clock of stepwise EM for a diagonal
+        Gaussian mixture on --batch planted points; --gmm_K, --gmm_dims).
 """
 from __future__ import annotations
 
@@ -232,6 +233,17 @@ def build(args, comm):
         return m, m.sweep, Ul * 64, "ratings/s", \
             dict(model=f"ALS-WR, k {args.als_k}, {synth.users} users x {synth.items} Zipf(1.05) items, 64 ratings a "
                        f"user, clocks of {args.batch or 4096} entities, fp32 rows", seq_len=None)
+    if args.model == "gmm":
+        from minips_amd.data.synthetic import GMMSynth
+        from minips_amd.models.gmm import GMM, GMMConfig
+
+        B = args.batch or 65536
+        synth = GMMSynth(B, dims=args.gmm_dims, K_teacher=args.gmm_K, sep=4.0, seed=3, device=dev)
+        m = GMM(GMMConfig(K=args.gmm_K, dims=args.gmm_dims, kappa=0.6, consistency=args.consistency,
+                          staleness=args.staleness), comm, init_data=synth.next())
+        data = synth.holdout(100 + r)
+        return m, (lambda: m.train_step(data.next())), B, "samples/s", \
+            dict(model=f"diagonal Gaussian mixture, stepwise EM, K={args.gmm_K} D={args.gmm_dims}", seq_len=None)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -310,7 +322,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
                                                          "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
-                                                         "gbdt", "lda", "w2v", "als"])
+                                                         "gbdt", "lda", "w2v", "als", "gmm"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -355,6 +367,8 @@ def main():
     ap.add_argument("--w2v_negatives", "--w2v-negatives", dest="w2v_negatives", type=int, default=5,
                     help="w2v: negatives per pair")
     ap.add_argument("--als_k", "--als-k", dest="als_k", type=int, default=32, help="als: factors")
+    ap.add_argument("--gmm_K", "--gmm-K", dest="gmm_K", type=int, default=64, help="gmm: components")
+    ap.add_argument("--gmm_dims", "--gmm-dims", dest="gmm_dims", type=int, default=64, help="gmm: dimensions")
     ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
                     help="gbdt: features (the teacher reads 5)")
     args = ap.parse_args()
