@@ -32,6 +32,8 @@
   extension, same rule.
 * ``_gmmk``     -- the Gaussian-mixture EM-step kernels (``ops.gmm_prepare`` / ``gmm_estep``): a fourteenth small
   torch extension, same rule.
+* ``_gmmfk``    -- the full-covariance Gaussian-mixture EM-step kernels (``ops.gmm_full_prepare`` /
+  ``gmm_full_estep``): a fifteenth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -137,6 +139,11 @@ def gmmk():
     return _load("_gmmk", "gfx950 HIP Gaussian-mixture EM-step kernels")
 
 
+def gmmfk():
+    """Return the HIP full-covariance Gaussian-mixture EM-step kernel module or raise a loud error."""
+    return _load("_gmmfk", "gfx950 HIP full-covariance Gaussian-mixture EM-step kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -196,6 +203,10 @@ def alsk_available() -> bool:
 
 def gmmk_available() -> bool:
     return _available(gmmk)
+
+
+def gmmfk_available() -> bool:
+    return _available(gmmfk)
 
 
 def native_dir() -> str:

@@ -421,9 +421,12 @@ class GMMSynth:
     ``sep`` N(0, 1) around a common offset, per-dimension standard deviations uniform in [0.5, 2] and weights
     proportional to U(0.5, 1.5), all drawn from ``seed`` alone (one teacher for every rank). next() returns X fp32
     [batch, dims]; ``labels`` holds the planted component of the last batch; holdout(seed) is an independent sample
-    stream of the same teacher; loglik(X) is the teacher's own mean log density in fp64."""
+    stream of the same teacher; loglik(X) is the teacher's own mean log density in fp64. ``rotate`` gives every
+    component a random rotation ``rot`` [K, D, D] of its own (covariance rot diag(sigma^2) rot^T), so the data is not
+    axis-aligned; the other draws are the same with and without it."""
 
-    def __init__(self, batch: int, dims: int = 8, K_teacher: int = 4, sep: float = 4.0, seed: int = 0, device="cpu"):
+    def __init__(self, batch: int, dims: int = 8, K_teacher: int = 4, sep: float = 4.0, seed: int = 0, device="cpu",
+                 rotate: bool = False):
         if batch < 1 or dims < 1 or K_teacher < 1 or sep < 0:
             raise ValueError(f"GMMSynth: batch {batch}, dims {dims}, K_teacher {K_teacher}, sep {sep}")
         self.batch, self.dims, self.K = batch, dims, K_teacher
@@ -436,6 +439,10 @@ class GMMSynth:
         self.weights = (w / w.sum()).to(self.device)
         self.gen = torch.Generator(device=self.device).manual_seed(seed + 2)
         self.labels = None
+        self.rot = None
+        if rotate:  # Q of a Gaussian matrix, from a generator of its own
+            gr = torch.Generator().manual_seed(seed + 3)
+            self.rot = torch.linalg.qr(torch.randn(K_teacher, dims, dims, generator=gr))[0].to(self.device)
 
     def holdout(self, seed: int) -> "GMMSynth":
         h = GMMSynth.__new__(GMMSynth)
@@ -447,10 +454,16 @@ class GMMSynth:
         z = torch.multinomial(self.weights, self.batch, replacement=True, generator=self.gen)
         self.labels = z
         eps = torch.randn(self.batch, self.dims, generator=self.gen, device=self.device)
-        return (self.centres[z] + self.sigma[z] * eps).float()
+        e = self.sigma[z] * eps
+        if self.rot is not None:
+            e = torch.einsum("nde,ne->nd", self.rot[z], e)
+        return (self.centres[z] + e).float()
 
     def loglik(self, X: torch.Tensor) -> float:
         x, mu, sd = X.double()[:, None, :], self.centres.double().to(X.device), self.sigma.double().to(X.device)
-        t = torch.log(self.weights.double().to(X.device)) - (0.5 * ((x - mu) / sd) ** 2 + torch.log(sd)).sum(2) \
+        e = x - mu
+        if self.rot is not None:
+            e = torch.einsum("kde,nkd->nke", self.rot.double().to(X.device), e)
+        t = torch.log(self.weights.double().to(X.device)) - (0.5 * (e / sd) ** 2 + torch.log(sd)).sum(2) \
             - 0.5 * self.dims * 1.8378770664093453
         return float(torch.logsumexp(t, 1).mean())

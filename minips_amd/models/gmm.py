@@ -15,6 +15,12 @@ batch EM. t is the table's own clock count (DenseTable.step, on the host, saved 
 and rolled back with the table), so a restored run continues with the step size of an uninterrupted one. Nothing is
 read back: a steady one-rank clock issues no host sync; the count of points that were skipped (non-finite lse) is
 read at drain(). The rule is stated in csrc/kernels/gmm.h.
+
+covariance="full" gives every component a full covariance matrix (the rule: csrc/kernels/gmm_full.h). The clock, the
+step size, the reduction and the checkpoints are the same; the table is K (D + D*D + 1) + D values, s [K, D + D*D + 1]
+(E[r_k x] | E[r_k x x^T] row-major | E[r_k]) followed by shift, the operands come from ops.gmm_full_prepare (a
+Cholesky factor's inverse per component, reg_covar added to the diagonal; var_floor is unused) and the E-step is
+ops.gmm_full_estep. The start is the seeding's centres with Sigma = diag(data variance). D <= 64.
 """
 from __future__ import annotations
 
@@ -41,8 +47,18 @@ class GMMConfig:
     seed: int = 0
     init_mode: str = "kmeans++"
     transport: str = "collective"
+    covariance: str = "diag"
+    reg_covar: float = 1e-6
 
     def __post_init__(self):
+        if self.covariance not in ("diag", "full"):
+            raise ValueError(f"gmm: unknown covariance {self.covariance!r}, expected 'diag' or 'full'")
+        if self.covariance == "full":
+            if not ops.gmm_full_shape_ok(self.K, self.dims):
+                raise ValueError(f"gmm: covariance 'full' with K = {self.K}, dims = {self.dims}, expected 1 <= K <= "
+                                 f"{ops.GMM_FULL_MAX_K} and 1 <= dims <= {ops.GMM_FULL_MAX_D}")
+            if not (self.reg_covar >= 0 and self.reg_covar < float("inf")):  # (a NaN fails the comparison)
+                raise ValueError(f"gmm: reg_covar is {self.reg_covar}, expected a finite value >= 0")
         if not ops.gmm_shape_ok(self.K, self.dims):
             raise ValueError(f"gmm: K = {self.K}, dims = {self.dims}, expected 1 <= K <= {ops.GMM_MAX_K}, 1 <= dims <= "
                              f"{ops.GMM_MAX_D} and 16 ceil(K / 16) * 16 ceil(dims / 16) <= {ops.GMM_MAX_KD}")
@@ -62,13 +78,15 @@ class GMM:
     def __init__(self, cfg: GMMConfig, comm: Comm, init_data: torch.Tensor | None = None):
         self.cfg, self.comm = cfg, comm
         K, D = cfg.K, cfg.dims
-        self.W = 2 * D + 1
+        self.full = cfg.covariance == "full"
+        self.W = ops.gmm_full_width(D) if self.full else 2 * D + 1
         dev = comm.device
         if dev.type == "cuda":  # a missing kernel is an error, here and not at the first clock
+            ext = "_gmmfk" if self.full else "_gmmk"
             try:
-                _native.gmmk()
+                _native.gmmfk() if self.full else _native.gmmk()
             except RuntimeError as e:
-                raise ValueError(f"gmm: the model runs on {dev} and needs the _gmmk extension: {e}") from e
+                raise ValueError(f"gmm: the model runs on {dev} and needs the {ext} extension: {e}") from e
         self.table = DenseTable(comm, K * self.W + D, optimizer="add", pull_dtype=torch.float32,
                                 consistency=cfg.consistency, staleness=cfg.staleness)
         if init_data is not None:
@@ -87,7 +105,11 @@ class GMM:
             centres = torch.randn(K, D, generator=torch.Generator().manual_seed(cfg.seed)).double()
             shift, var = torch.zeros(D, dtype=torch.float64), torch.ones(D, dtype=torch.float64)
         mu = centres - shift
-        s = torch.cat([mu, var + mu * mu, torch.ones(K, 1, dtype=torch.float64)], 1) / K
+        if self.full:
+            S2 = torch.diag(var)[None] + mu[:, :, None] * mu[:, None, :]
+            s = torch.cat([mu, S2.reshape(K, D * D), torch.ones(K, 1, dtype=torch.float64)], 1) / K
+        else:
+            s = torch.cat([mu, var + mu * mu, torch.ones(K, 1, dtype=torch.float64)], 1) / K
         self.table.load_full(torch.cat([s.reshape(-1), shift]).float())
         self.bad = torch.zeros(1, dtype=torch.int32, device=dev)
         self.bad_total = 0       # points skipped for a non-finite lse, as of the last drain()
@@ -102,14 +124,18 @@ class GMM:
         P = self.table.get()
         return P[: K * W].view(K, W), P[K * W: K * W + D]
 
+    def _estep(self, X, **kw):
+        s, shift = self._state()
+        if self.full:
+            return s, ops.gmm_full_estep(X, shift, *ops.gmm_full_prepare(s, self.cfg.reg_covar), **kw)
+        return s, ops.gmm_estep(X, shift, *ops.gmm_prepare(s, self.cfg.var_floor), **kw)
+
     def train_step(self, X):
         """X [B, D] fp32, the same B on every rank. Returns the batch's summed log-likelihood (fp64 [1], before the
         update)."""
         X = self._points(X)
         cfg, K, W = self.cfg, self.cfg.K, self.W
-        s, shift = self._state()
-        coef, cst = ops.gmm_prepare(s, cfg.var_floor)
-        S, ll, _, _ = ops.gmm_estep(X, shift, coef, cst, bad=self.bad)
+        s, (S, ll, _, _) = self._estep(X, bad=self.bad)
         rho = cfg.rho0 * (self.table.step + cfg.t0) ** -cfg.kappa  # the table's clock count: checkpoints carry it
         world = self.comm.world
         G = self.table.grad
@@ -122,15 +148,19 @@ class GMM:
     def predict(self, X):
         """(assign int32 [n], logp fp32 [n]): the most responsible component and the log density of every point."""
         X = self._points(X)
-        s, shift = self._state()
-        coef, cst = ops.gmm_prepare(s, self.cfg.var_floor)
-        _, _, assign, logp = ops.gmm_estep(X, shift, coef, cst, accumulate=False, want_assign=True, want_logp=True)
+        _, (_, _, assign, logp) = self._estep(X, accumulate=False, want_assign=True, want_logp=True)
         return assign, logp
 
     def params(self):
-        """(pi [K], mu [K, D], var [K, D]) in the points' own coordinates (torch code, not the hot path)."""
+        """(pi [K], mu [K, D], var [K, D]) in the points' own coordinates (torch code, not the hot path); in full mode
+        the third value is cov [K, D, D]."""
         s, shift = self._state()
         D = self.cfg.dims
+        if self.full:
+            s0 = s[:, -1]
+            mu = s[:, :D] / s0[:, None]
+            cov = s[:, D:D + D * D].reshape(-1, D, D) / s0[:, None, None] - mu[:, :, None] * mu[:, None, :]
+            return s0 / s0.sum(), mu + shift, cov + self.cfg.reg_covar * torch.eye(D, device=s.device)
         s0 = s[:, 2 * D]
         mu = s[:, :D] / s0[:, None]
         var = (s[:, D:2 * D] / s0[:, None] - mu * mu).clamp(min=self.cfg.var_floor)

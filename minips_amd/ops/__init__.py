@@ -13,7 +13,8 @@ import math
 
 import torch
 
-from .._native import alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmk, kernels, ldak, optk, w2vk, wdftrlk
+from .._native import (alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, kernels, ldak, optk, w2vk,
+                       wdftrlk)
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -2039,6 +2040,117 @@ def gmm_estep(X, shift, coef, cst, accumulate=True, want_assign=False, want_logp
     r = torch.where(ok[:, None], torch.exp(t - lse[:, None]), torch.zeros(()))
     x = torch.where(ok[:, None], x, torch.zeros(()))
     S = torch.cat([r.t() @ x, r.t() @ (x * x), r.sum(0)[:, None]], 1) if accumulate else None
+    ll = torch.where(ok, lse, torch.zeros(())).double().sum().reshape(1)
+    if bad is not None:
+        bad += int((~ok).sum())
+    assign = None
+    if want_assign:  # the lowest index among the maxima
+        first = torch.where(t == m[:, None], torch.arange(K), torch.full((), K)).min(1).values
+        assign = torch.where(ok, first, torch.full((), -1)).to(torch.int32)
+    logp = torch.where(ok, lse, torch.full((), float("nan"))) if want_logp else None
+    return S, ll, assign, logp
+
+
+# ----------------------------------------------------------------------------- GMM with full covariances
+# csrc/kernels/gmm_full.h (the binding exports them too)
+GMM_FULL_MAX_K, GMM_FULL_MAX_D, GMM_FULL_CHUNK, GMM_FULL_MAX_CHUNKS, GMM_FULL_PART_CAP = 128, 64, 2048, 256, 1 << 26
+
+
+def gmm_full_shape_ok(K: int, D: int) -> bool:
+    return 1 <= K <= GMM_FULL_MAX_K and 1 <= D <= GMM_FULL_MAX_D
+
+
+def gmm_full_width(D: int) -> int:
+    return D + D * D + 1
+
+
+def gmm_full_chunk(n: int, K: int, D: int) -> int:
+    """The chunk length of gmm_full_estep's partials, a function of (n, K, D) only (gmm_full.h: Bits)."""
+    base = (n + GMM_FULL_CHUNK - 1) // GMM_FULL_CHUNK
+    cap = min(GMM_FULL_MAX_CHUNKS, GMM_FULL_PART_CAP // (K * gmm_full_width(D)))
+    return GMM_FULL_CHUNK * (1 if base <= cap else (base + cap - 1) // cap)
+
+
+def _gmm_full_check(op, K, D):
+    if not gmm_full_shape_ok(K, D):
+        raise ValueError(f"gmm: {op}: K = {K}, D = {D}, expected 1 <= K <= {GMM_FULL_MAX_K} and 1 <= D <= "
+                         f"{GMM_FULL_MAX_D}")
+
+
+def gmm_full_prepare(s, reg_covar: float = 1e-6):
+    """The full-covariance E-step's operands from the normalised sufficient statistics s fp32 [K, D + D*D + 1] (the
+    rule: csrc/kernels/gmm_full.h): Wh fp32 [K, DP, DP] = L^-1 of Sigma = S2 / s0 - mu mu^T + reg_covar I = L L^T (lower
+    triangular, pads 0), b fp32 [K, DP] = Wh mu and cst fp32 [K] = log pi - sum log L_dd - D / 2 log 2 pi. A component
+    with s0 <= 0, a non-finite statistic, a non-positive pivot or a non-finite cst is dead: cst = -inf, Wh and b 0. On
+    the GPU one gfx950 launch, a workgroup per component; the CPU path is the fp32 PyTorch reference of the same
+    rule."""
+    D = int(math.isqrt(max(s.shape[1] - 1, 0))) if s.dim() == 2 else 0
+    if s.dim() != 2 or D < 1 or s.shape[1] != gmm_full_width(D) or s.dtype != torch.float32:
+        raise ValueError(f"gmm: gmm_full_prepare takes s fp32 [K, D + D*D + 1], got {s.dtype} {tuple(s.shape)}")
+    K = s.shape[0]
+    _gmm_full_check("gmm_full_prepare", K, D)
+    if not (reg_covar >= 0 and reg_covar < float("inf")):
+        raise ValueError(f"gmm: reg_covar is {reg_covar}, expected a finite value >= 0")
+    dp = gmm_pad(D)
+    if _gpu(s):
+        Wh = torch.empty(K, dp, dp, dtype=torch.float32, device=s.device)
+        b = torch.empty(K, dp, dtype=torch.float32, device=s.device)
+        cst = torch.empty(K, dtype=torch.float32, device=s.device)
+        gmmfk().gmm_full_prepare(s.contiguous(), D, float(reg_covar), Wh, b, cst)
+        return Wh, b, cst
+    s0, s1, S2 = s[:, -1], s[:, :D], s[:, D:D + D * D].reshape(K, D, D)
+    live0 = torch.isfinite(s0) & (s0 > 0)
+    tot = torch.where(live0, s0, torch.zeros(())).sum()
+    mu = s1 / s0[:, None]
+    sigma = S2 / s0[:, None, None] - mu[:, :, None] * mu[:, None, :] + float(reg_covar) * torch.eye(D)
+    sigma = torch.where(torch.isfinite(sigma), sigma, torch.zeros(()))
+    L, info = torch.linalg.cholesky_ex(sigma)  # reads the lower triangle
+    L = torch.where((info == 0)[:, None, None], L, torch.eye(D).expand(K, D, D))
+    Wi = torch.linalg.solve_triangular(L, torch.eye(D).expand(K, D, D), upper=False)
+    cst = torch.log(s0 / tot) - torch.log(torch.diagonal(L, dim1=1, dim2=2)).sum(1) - 0.5 * D * _GMM_LOG_2PI
+    dead = ~live0 | ~torch.isfinite(s).all(1) | (info != 0) | ~torch.isfinite(cst)
+    Wh, b = torch.zeros(K, dp, dp, dtype=torch.float32), torch.zeros(K, dp, dtype=torch.float32)
+    Wh[:, :D, :D] = torch.where(dead[:, None, None], torch.zeros(()), torch.tril(Wi))
+    b[:, :D] = (Wh[:, :D, :D] @ torch.where(dead[:, None], torch.zeros(()), mu)[:, :, None])[:, :, 0]
+    return Wh, b, torch.where(dead, torch.full((), float("-inf")), cst)
+
+
+def gmm_full_estep(X, shift, Wh, b, cst, accumulate=True, want_assign=False, want_logp=False, bad=None, blocks=0):
+    """The E-step of a full-covariance Gaussian mixture over the points X fp32 [n, D] (row stride >= D; the rule:
+    csrc/kernels/gmm_full.h), x = X - shift: y_k = Wh_k x - b_k, t_ik = cst_k - 0.5 |y_k|^2, lse_i = logsumexp_k t_ik,
+    r_ik = exp(t_ik - lse_i). Returns (S, ll, assign, logp) as gmm_estep does, with S fp32 [K, D + D*D + 1] = the sums
+    over i of r x | r x x^T (symmetric to the bit) | r. On the GPU a scores launch, a statistics launch and a fold
+    launch, scores and statistics by fp32 MFMA, no float atomics, the same bits on every run and for every grid size
+    (``blocks``); the CPU path is the fp32 PyTorch reference."""
+    if X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError(f"gmm: gmm_full_estep takes fp32 points [n, D], got {X.dtype} {tuple(X.shape)}")
+    n, D, K = X.shape[0], shift.numel(), cst.numel()
+    _gmm_full_check("gmm_full_estep", K, D)
+    dp = gmm_pad(D)
+    if X.shape[1] != D or tuple(Wh.shape) != (K, dp, dp) or tuple(b.shape) != (K, dp):
+        raise ValueError(f"gmm: gmm_full_estep: X {tuple(X.shape)}, shift [{D}], Wh {tuple(Wh.shape)}, b "
+                         f"{tuple(b.shape)}, cst [{K}]: expected X [n, {D}], Wh [{K}, {dp}, {dp}] and b [{K}, {dp}]")
+    dev = X.device
+    if _gpu(X):
+        S = torch.empty(K, gmm_full_width(D), dtype=torch.float32, device=dev) if accumulate else None
+        ll = torch.empty(1, dtype=torch.float64, device=dev)
+        assign = torch.empty(n, dtype=torch.int32, device=dev) if want_assign else None
+        logp = torch.empty(n, dtype=torch.float32, device=dev) if want_logp else None
+        gmmfk().gmm_full_estep(X, shift, Wh, b, cst, S, ll, assign, logp, bad, int(blocks))
+        return S, ll, assign, logp
+    x = X - shift
+    y = torch.einsum("kjd,nd->nkj", Wh[:, :D, :D], x) - b[:, :D]
+    t = cst - 0.5 * (y * y).sum(2)
+    m = torch.where(torch.isnan(t), torch.full((), float("-inf")), t).max(1).values
+    lse = m + torch.log(torch.exp(t - m[:, None]).sum(1))
+    ok = torch.isfinite(lse)
+    S = None
+    if accumulate:
+        r = torch.where(ok[:, None], torch.exp(t - lse[:, None]), torch.zeros(()))
+        x = torch.where(ok[:, None], x, torch.zeros(()))
+        S2 = torch.tril(torch.einsum("nk,nd,ne->kde", r, x, x))  # the lower triangle, mirrored
+        S2 = S2 + torch.tril(S2, -1).transpose(1, 2)
+        S = torch.cat([r.t() @ x, S2.reshape(K, D * D), r.sum(0)[:, None]], 1)
     ll = torch.where(ok, lse, torch.zeros(())).double().sum().reshape(1)
     if bad is not None:
         bad += int((~ok).sum())

@@ -38,7 +38,9 @@ collective BSP only.
 --model gmm is a diagonal Gaussian mixture fitted by stepwise EM (models/gmm.py): --K components over --num_dims
 dimensions, points from a planted mixture (GMMSynth) or an --input libsvm file densified a batch at a time (refused
 above 128 features); --gmm_rho0 / --gmm_kappa / --gmm_var_floor, --kmeans_init_mode seeds the centres; the reported
-loss is the batch's mean log-likelihood; the final JSON gains gmm_K and gmm_loglik, collective only.
+loss is the batch's mean log-likelihood; the final JSON gains gmm_K and gmm_loglik, collective only. --gmm_covariance
+full fits a full covariance matrix per component (--num_dims <= 64, --gmm_reg_covar on the diagonal; the synthetic
+teacher is then rotated) and adds gmm_covariance to the final JSON.
 On --use_weight_file the tables restore from the checkpoint and training resumes at the saved
 iteration with the data stream advanced to the same position, so a restarted run ends with the
 same parameters as an uninterrupted one (BSP).
@@ -209,6 +211,10 @@ def parse(argv=None):
     ap.add_argument("--gmm_kappa", type=float, default=None,
                     help="gmm: the step's decay exponent in [0, 1] (default 0.6)")
     ap.add_argument("--gmm_var_floor", type=float, default=None, help="gmm: the variance floor > 0 (default 1e-4)")
+    ap.add_argument("--gmm_covariance", choices=["diag", "full"], default=None,
+                    help="gmm: a diagonal or a full covariance matrix per component (default diag)")
+    ap.add_argument("--gmm_reg_covar", type=float, default=None,
+                    help="gmm: --gmm_covariance full adds this to every covariance's diagonal, >= 0 (default 1e-6)")
     ap.add_argument("--als_k", type=int, default=None, help="als: factors, a multiple of 4 in [4, 128] (default 8 with "
                                                             "--small, else 32)")
     ap.add_argument("--als_reg", type=float, default=None, help="als: lambda > 0 (default 0.05)")
@@ -414,19 +420,28 @@ def parse(argv=None):
             ap.error("--model als: no --eval_every (every sweep reports the held-out RMSE)")
     elif als_flags:
         ap.error(f"{' / '.join(als_flags)}: --model als only, not {args.model}")
-    gmm_flags = [f"--{k}" for k in ("gmm_rho0", "gmm_kappa", "gmm_var_floor") if getattr(args, k) is not None]
+    gmm_flags = [f"--{k}" for k in ("gmm_rho0", "gmm_kappa", "gmm_var_floor", "gmm_covariance",
+                                          "gmm_reg_covar") if getattr(args, k) is not None]
     if args.model == "gmm":
         from .ops import GMM_MAX_D, gmm_shape_ok
 
         args.gmm_rho0 = 1.0 if args.gmm_rho0 is None else args.gmm_rho0
         args.gmm_kappa = 0.6 if args.gmm_kappa is None else args.gmm_kappa  # a stream of batches: a decaying step
         args.gmm_var_floor = 1e-4 if args.gmm_var_floor is None else args.gmm_var_floor
+        if args.gmm_reg_covar is not None and args.gmm_covariance != "full":
+            ap.error("--gmm_reg_covar: --gmm_covariance full only")
+        args.gmm_covariance = args.gmm_covariance or "diag"
+        args.gmm_reg_covar = 1e-6 if args.gmm_reg_covar is None else args.gmm_reg_covar
+        if not 0 <= args.gmm_reg_covar < float("inf"):
+            ap.error(f"--model gmm: --gmm_reg_covar {args.gmm_reg_covar} must be a finite value >= 0")
         args.K = args.K or (4 if args.small else 64)
         if not args.input:
             args.num_dims = args.num_dims or (8 if args.small else 64)
         if args.num_dims and not gmm_shape_ok(args.K, args.num_dims):
             ap.error(f"--model gmm: --K {args.K} and --num_dims {args.num_dims} must lie in [1, 128] with "
                      f"16 ceil(K / 16) * 16 ceil(D / 16) <= 8192")
+        if args.gmm_covariance == "full" and args.num_dims > 64:
+            ap.error(f"--model gmm: --gmm_covariance full needs --num_dims {args.num_dims} <= 64")
         if not 1 <= args.K <= 128 or args.num_dims > GMM_MAX_D:
             ap.error(f"--model gmm: --K {args.K} must lie in [1, 128] and --num_dims {args.num_dims} in [1, 128] (an "
                      f"--input file is densified)")
@@ -882,7 +897,8 @@ def build(args, comm):
         def gmm_cfg(D):
             return GMMConfig(K=args.K, dims=D, var_floor=args.gmm_var_floor, rho0=args.gmm_rho0, kappa=args.gmm_kappa,
                              consistency=args.consistency, staleness=args.staleness, seed=seed,
-                             init_mode=args.kmeans_init_mode or "kmeans++")
+                             init_mode=args.kmeans_init_mode or "kmeans++", covariance=args.gmm_covariance,
+                             reg_covar=args.gmm_reg_covar)
 
         if args.input:  # every libsvm batch is densified with torch: an absent feature is 0.0
             shard = args._shard.to(dev)
@@ -911,7 +927,8 @@ def build(args, comm):
 
         B = args.batch or (256 if args.small else 65536)
         # one teacher for every rank (seed), this rank's own sample stream; seeding reads its own batch
-        synth = GMMSynth(B, dims=args.num_dims, K_teacher=args.K, sep=4.0, seed=args.seed, device=dev)
+        synth = GMMSynth(B, dims=args.num_dims, K_teacher=args.K, sep=4.0, seed=args.seed, device=dev,
+                         rotate=args.gmm_covariance == "full")
         m = GMM(gmm_cfg(args.num_dims), comm, init_data=synth.holdout(seed + 7919).next())
         args._gmm_hold = synth.holdout(args.seed + 104729).next()  # the same held-out points on every rank
         return m, {0: m.table}, (lambda: _Skippable(synth.holdout(seed + 1))), (lambda b: m.train_step(b)), B
@@ -1383,6 +1400,8 @@ def main(argv=None):
     if args.model == "gmm":  # the mean log density of the held-out points (the seeding batch with --input)
         ftrl_final.update(gmm_K=model.cfg.K,
                           gmm_loglik=round(float(model.predict(args._gmm_hold)[1].double().mean()), 6))
+        if model.full:
+            ftrl_final.update(gmm_covariance="full")
     if args.model == "w2v":  # vectors() is a collective Get; the purity of the planted groups is read on the host
         ftrl_final.update(w2v_dim=model.d, w2v_pairs=model.total_pairs)
         if args._w2v_group:

@@ -18,7 +18,8 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         word2vec skip-gram with negative sampling on --batch pairs of Zipf words; --w2v_dim, --w2v_negatives), als
         (a sweep of alternating least squares over 131072 users x 32768 Zipf items per rank, 64 ratings a user,
         clocks of --batch entities; --als_k; ms_per_step is ms per sweep), gmm (a clock of stepwise EM for a diagonal
-        Gaussian mixture on --batch planted points; --gmm_K, --gmm_dims).
+        Gaussian mixture on --batch planted points; --gmm_K, --gmm_dims; --gmm_covariance full for full covariance
+        matrices on rotated planted points).
 """
 from __future__ import annotations
 
@@ -238,12 +239,14 @@ def build(args, comm):
         from minips_amd.models.gmm import GMM, GMMConfig
 
         B = args.batch or 65536
-        synth = GMMSynth(B, dims=args.gmm_dims, K_teacher=args.gmm_K, sep=4.0, seed=3, device=dev)
+        full = args.gmm_covariance == "full"
+        synth = GMMSynth(B, dims=args.gmm_dims, K_teacher=args.gmm_K, sep=4.0, seed=3, device=dev, rotate=full)
         m = GMM(GMMConfig(K=args.gmm_K, dims=args.gmm_dims, kappa=0.6, consistency=args.consistency,
-                          staleness=args.staleness), comm, init_data=synth.next())
+                          staleness=args.staleness, covariance=args.gmm_covariance), comm, init_data=synth.next())
         data = synth.holdout(100 + r)
         return m, (lambda: m.train_step(data.next())), B, "samples/s", \
-            dict(model=f"diagonal Gaussian mixture, stepwise EM, K={args.gmm_K} D={args.gmm_dims}", seq_len=None)
+            dict(model=f"{'full-covariance' if full else 'diagonal'} Gaussian mixture, stepwise EM, K={args.gmm_K} "
+                       f"D={args.gmm_dims}", seq_len=None)
     if args.model == "kmeans":
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
@@ -369,6 +372,8 @@ def main():
     ap.add_argument("--als_k", "--als-k", dest="als_k", type=int, default=32, help="als: factors")
     ap.add_argument("--gmm_K", "--gmm-K", dest="gmm_K", type=int, default=64, help="gmm: components")
     ap.add_argument("--gmm_dims", "--gmm-dims", dest="gmm_dims", type=int, default=64, help="gmm: dimensions")
+    ap.add_argument("--gmm_covariance", "--gmm-covariance", dest="gmm_covariance", choices=["diag", "full"],
+                    default="diag", help="gmm: diagonal or full covariance matrices")
     ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
                     help="gbdt: features (the teacher reads 5)")
     args = ap.parse_args()
