@@ -34,6 +34,8 @@
   torch extension, same rule.
 * ``_gmmfk``    -- the full-covariance Gaussian-mixture EM-step kernels (``ops.gmm_full_prepare`` /
   ``gmm_full_estep``): a fifteenth small torch extension, same rule.
+* ``_ibsk``     -- the in-batch sampled softmax kernels of the two-tower model (``ops.ibs_forward`` /
+  ``ibs_backward``): a sixteenth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -144,6 +146,11 @@ def gmmfk():
     return _load("_gmmfk", "gfx950 HIP full-covariance Gaussian-mixture EM-step kernels")
 
 
+def ibsk():
+    """Return the HIP in-batch sampled softmax kernel module or raise a loud error."""
+    return _load("_ibsk", "gfx950 HIP in-batch sampled softmax kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -207,6 +214,10 @@ def gmmk_available() -> bool:
 
 def gmmfk_available() -> bool:
     return _available(gmmfk)
+
+
+def ibsk_available() -> bool:
+    return _available(ibsk)
 
 
 def native_dir() -> str:

@@ -467,3 +467,39 @@ class GMMSynth:
         t = torch.log(self.weights.double().to(X.device)) - (0.5 * (e / sd) ** 2 + torch.log(sd)).sum(2) \
             - 0.5 * self.dims * 1.8378770664093453
         return float(torch.logsumexp(t, 1).mean())
+
+
+class PairSynth:
+    """(user, item) pairs for the two-tower model (models/twotower.py) from a fixed teacher: U* [users, k_teacher]
+    and V* [items, k_teacher] ~ N(0, 1 / sqrt(k_teacher)), popularity_i proportional to (i + 1)^-zipf. next() draws
+    ``batch`` users uniformly and every user's item from softmax_i(scale <U*_u, V*_i> + log popularity_i); it returns
+    (users, items) int64 [batch]. holdout(seed) is an independent pair stream of the same teacher; item_counts() is
+    the items' marginal draw probability over all users as int64 counts out of 2^20 draws (what a pass over a long
+    log would count). Generated on the host from ``seed`` alone."""
+
+    def __init__(self, users: int = 256, items: int = 128, k_teacher: int = 4, batch: int = 128, seed: int = 0,
+                 zipf: float = 0.0, scale: float = 3.0):
+        if users < 1 or items < 1 or k_teacher < 1 or batch < 1 or zipf < 0 or scale < 0:
+            raise ValueError(f"PairSynth: users {users}, items {items}, k_teacher {k_teacher}, batch {batch}, zipf "
+                             f"{zipf}, scale {scale}")
+        self.users, self.items, self.batch, self.seed = users, items, batch, seed
+        g = torch.Generator().manual_seed(seed + 1)
+        self.U = torch.randn(users, k_teacher, generator=g, dtype=torch.float64) / k_teacher ** 0.25
+        self.V = torch.randn(items, k_teacher, generator=g, dtype=torch.float64) / k_teacher ** 0.25
+        pop = torch.arange(1, items + 1, dtype=torch.float64).pow(-zipf)
+        self.probs = torch.softmax(scale * self.U @ self.V.t() + torch.log(pop)[None, :], 1)  # [users, items]
+        self.gen = torch.Generator().manual_seed(seed + 2)
+
+    def holdout(self, seed: int) -> "PairSynth":
+        h = PairSynth.__new__(PairSynth)
+        h.__dict__.update(self.__dict__)
+        h.gen = torch.Generator().manual_seed(self.seed + 7919 * (seed + 1))
+        return h
+
+    def next(self):
+        u = torch.randint(0, self.users, (self.batch,), generator=self.gen)
+        i = torch.multinomial(self.probs[u], 1, generator=self.gen).reshape(-1)
+        return u, i
+
+    def item_counts(self) -> torch.Tensor:
+        return torch.round(self.probs.mean(0) * float(1 << 20)).to(torch.int64)

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from .._native import (alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, kernels, ldak, optk, w2vk,
+from .._native import (alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, ldak, optk, w2vk,
                        wdftrlk)
 
 EPI_STORE_F32 = 0
@@ -1954,6 +1954,127 @@ def als_gram(rows, k=None):
     _als_check("als_gram", k, rows)
     Y = rows[:, :k]
     return Y.t() @ Y
+
+
+# ----------------------------------------------------------------------------- two-tower: in-batch sampled softmax
+IBS_MIN_D, IBS_MAX_D, IBS_TILE = 8, 128, 64  # csrc/kernels/ibs.h (the binding exports them too)
+_IBS_ROWS = 2048  # queries per pass of the CPU references
+
+
+def _ibs_check(op, inv, rows, d, tau, logq, blocks=0):
+    if d % 4 or not IBS_MIN_D <= d <= IBS_MAX_D:
+        raise RuntimeError(f"{op}: d is {d}, expected d % 4 == 0 and {IBS_MIN_D} <= d <= {IBS_MAX_D}")
+    if not (tau > 0 and math.isfinite(tau)):
+        raise RuntimeError(f"{op}: tau is {tau}, expected a positive finite temperature")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[1] < d:
+        raise RuntimeError(f"{op}: rows must be fp32 [cap, >= {d}], got {rows.dtype} {tuple(rows.shape)}")
+    if inv.dim() != 1 or inv.numel() % 2 or inv.dtype != torch.int64:
+        raise RuntimeError(f"{op}: inv must be int64 [2 P], got {inv.dtype} {tuple(inv.shape)}")
+    if logq is not None and (logq.dim() != 1 or logq.numel() != inv.numel() // 2):
+        raise RuntimeError(f"{op}: logq has shape {tuple(logq.shape)}, expected [{inv.numel() // 2}]")
+    if not 0 <= blocks <= 65535:
+        raise RuntimeError(f"{op}: blocks is {blocks}, expected 0 <= blocks <= 65535")
+
+
+def _ibs_sides(inv, rows, d):
+    """(valid [P], item rows [P], A [P, d], B [P, d]) of the rule: the rows of an invalid pair are zero."""
+    cap = rows.shape[0]
+    iv = inv.view(-1, 2)
+    u, it = iv[:, 0], iv[:, 1]
+    valid = (u >= 0) & (u < cap) & (it >= 0) & (it < cap)
+    if cap == 0:
+        z = torch.zeros(iv.shape[0], d, dtype=rows.dtype)
+        return valid, it, z, z.clone()
+    A = rows[u.clamp(0, cap - 1)][:, :d] * valid[:, None]
+    B = rows[it.clamp(0, cap - 1)][:, :d] * valid[:, None]
+    return valid, it, A, B
+
+
+def _ibs_logits(lo, hi, valid, it, A, B, rtau, logq):
+    """(s [hi - lo, P] with the candidates that are not live at -inf, the diagonal's column index)."""
+    P = valid.numel()
+    s = (A[lo:hi] @ B.t()) * rtau
+    if logq is not None:
+        s = s - logq[None, :]
+    me = torch.arange(lo, hi)
+    live = valid[lo:hi, None] & valid[None, :] & ((me[:, None] == torch.arange(P)[None, :]) |
+                                                  (it[lo:hi, None] != it[None, :]))
+    return s.masked_fill(~live, -math.inf), me
+
+
+def ibs_forward(inv, rows, d, tau, logq=None, gscale=1.0, blocks=0):
+    """The in-batch sampled softmax of a batch of P (user, item) pairs over pulled rows (the rule:
+    csrc/kernels/ibs.h). inv int64 [2 P] are a plan's row indices of the key matrix [P, 2], rows fp32 [cap, >= d],
+    logq fp32 [P] or None the log sampling probability of every pair's item. With a_p = rows[inv[2 p]], b_q =
+    rows[inv[2 q + 1]]: s_pq = <a_p, b_q> / tau - logq_q, lse_p = log sum exp s_pq over the live candidates q (valid
+    pairs; another pair that carries p's own item is left out), loss_p = lse_p - s_pp. A pair with an inv outside
+    [0, cap) is neither query nor candidate and gets loss = lse = 0. Returns fp32 (loss [P], lse [P]); ``gscale``
+    scales only the gradient (ibs_backward). One fused gfx950 launch on the GPU (fp32 MFMA, no P x P traffic, the
+    same bits for every grid size, ``blocks``); the CPU path is the fp32 PyTorch reference of the same rule."""
+    d, tau, P = int(d), float(tau), inv.numel() // 2
+    if _gpu(rows):
+        lse = torch.empty(P, dtype=torch.float32, device=rows.device)
+        loss = torch.empty(P, dtype=torch.float32, device=rows.device)
+        ibsk().ibs_forward(inv, rows, d, tau, logq, lse, loss, int(blocks))
+        return loss, lse
+    _ibs_check("ibs_forward", inv, rows, d, tau, logq, blocks)
+    loss, lse = torch.zeros(P, dtype=torch.float32), torch.zeros(P, dtype=torch.float32)
+    valid, it, A, B = _ibs_sides(inv, rows, d)
+    rtau = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(tau, dtype=torch.float32)
+    for lo in range(0, P, _IBS_ROWS):
+        hi = min(lo + _IBS_ROWS, P)
+        s, me = _ibs_logits(lo, hi, valid, it, A, B, rtau, logq)
+        v = valid[lo:hi]
+        l = torch.where(v, torch.logsumexp(s, 1), torch.zeros(()))
+        lse[lo:hi] = l
+        loss[lo:hi] = torch.where(v, l - s[torch.arange(hi - lo), me], torch.zeros(()))
+    return loss, lse
+
+
+def ibs_backward(inv, rows, d, tau, lse, grad_rows, logq=None, gscale=1.0, csr=None, blocks=0):
+    """Gradient of every unique pulled row of ibs_forward's batch (csrc/kernels/ibs.h): G_pq = (exp(s_pq - lse_p) -
+    [p == q]) gscale / tau over the live candidates, dA_p = sum_q G_pq b_q, dB_q = sum_p G_pq a_p, and grad_rows[u]
+    = the sum over the lookups of row u of their dA (user lookups) or dB (item lookups) rows; rows without lookups
+    are left untouched. ``lse`` is ibs_forward's on the same inputs, ``csr`` = (members, memrow) the lookups grouped
+    by unique row (a plan's lookup CSR; built from ``inv`` here when absent on the GPU, ignored on the CPU). On the
+    GPU two fused MFMA sweeps recompute the logit tiles (one with the users resident, one with the items) and a
+    row reduce writes every row exactly once in member order -- no atomics, the same bits on every run and for every
+    grid size (``blocks``); the CPU reference sums with index_add_ over ``inv``."""
+    d, tau, P = int(d), float(tau), inv.numel() // 2
+    if _gpu(rows):
+        if csr is None:  # (not the model's path) rows outside [0, cap) go to a row past the end, which the kernel
+            cap = rows.shape[0]  # ignores: emb_build_csr trusts its rows
+            ok = (inv >= 0) & (inv < cap)
+            csr = emb_build_csr(torch.where(ok, inv, torch.full_like(inv, cap)), 1, cap + 1)
+        ibsk().ibs_backward(csr[0], csr[1], inv, rows, d, tau, logq, lse, float(gscale), grad_rows, int(blocks))
+        return grad_rows
+    _ibs_check("ibs_backward", inv, rows, d, tau, logq, blocks)
+    cap = rows.shape[0]
+    if lse.numel() != P or grad_rows.dim() != 2 or grad_rows.shape[1] != d or grad_rows.shape[0] < cap:
+        raise RuntimeError(f"ibs_backward: lse [{lse.numel()}], grad_rows {tuple(grad_rows.shape)} for {P} pairs of "
+                           f"rows {tuple(rows.shape)}")
+    if P == 0 or cap == 0:
+        return grad_rows
+    valid, it, A, B = _ibs_sides(inv, rows, d)
+    rtau = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(tau, dtype=torch.float32)
+    gs = torch.tensor(float(gscale) / tau, dtype=torch.float32)
+    dA, dB = torch.zeros(P, d, dtype=torch.float32), torch.zeros(P, d, dtype=torch.float32)
+    for lo in range(0, P, _IBS_ROWS):
+        hi = min(lo + _IBS_ROWS, P)
+        s, me = _ibs_logits(lo, hi, valid, it, A, B, rtau, logq)
+        G = torch.exp(s - lse[lo:hi, None])
+        G[torch.arange(hi - lo), me] -= valid[lo:hi].float()
+        G *= gs
+        dA[lo:hi] = G @ B
+        dB += G.t() @ A[lo:hi]
+    acc = torch.zeros(cap, d, dtype=torch.float32)
+    iv = inv.view(P, 2)
+    acc.index_add_(0, iv[valid, 0], dA[valid])
+    acc.index_add_(0, iv[valid, 1], dB[valid])
+    touched = torch.zeros(cap, dtype=torch.bool)
+    touched[inv[(inv >= 0) & (inv < cap)]] = True
+    grad_rows[:cap][touched] = acc[touched]
+    return grad_rows
 
 
 # ----------------------------------------------------------------------------- GMM: Gaussian mixture by EM

@@ -29,6 +29,10 @@ resident corpus -- --w2v_sentences synthetic sentences of --w2v_len tokens over 
 libsvm file whose lines are sentences in file order (`label word:x ...`, ids minus one, values ignored);
 --w2v_dim / --w2v_negatives / --w2v_window / --w2v_sample / --w2v_vocab, --batch pairs per clock; the reported loss
 is the epoch's mean pair loss; the final JSON gains w2v_dim, w2v_pairs and (synthetic) w2v_purity, collective only.
+--model twotower is two-tower retrieval with the in-batch sampled softmax (models/twotower.py): --batch pairs per
+clock from a fixed teacher (PairSynth, --tt_users x --tt_items), --tt_dim / --tt_tau, --tt_no_bias_correction leaves
+the logits uncorrected; --eval_every reports the held-out in-batch loss; the final JSON gains tt_dim and tt_tau,
+collective only.
 --model als is collaborative filtering by alternating least squares (models/als.py): --steps counts sweeps (the
 user half, then the item half) over a resident rating matrix -- --als_users x --als_items synthetic low-rank ratings,
 --als_per_user a user (MFSynth), every rank an even slice of each side, or on one rank an --input libsvm file whose
@@ -67,7 +71,7 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
                                                              "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v", "als",
-                                                             "gmm"])
+                                                             "gmm", "twotower"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -193,6 +197,13 @@ def parse(argv=None):
                     help="lda, synthetic data: documents over all ranks (default 256 with --small, else 65536)")
     ap.add_argument("--lda_doc_len", type=int, default=None,
                     help="lda, synthetic data: tokens per document, 1..4096 (default 48 with --small, else 128)")
+    ap.add_argument("--tt_dim", type=int, default=None, help="twotower: embedding width, a multiple of 4 in [8, 128] "
+                                                            "(default 16 with --small, else 64)")
+    ap.add_argument("--tt_tau", type=float, default=None, help="twotower: softmax temperature > 0 (default 0.1)")
+    ap.add_argument("--tt_users", type=int, default=None, help="twotower: users (default 256 with --small, else 65536)")
+    ap.add_argument("--tt_items", type=int, default=None, help="twotower: items (default 128 with --small, else 16384)")
+    ap.add_argument("--tt_no_bias_correction", action="store_true", default=None,
+                    help="twotower: do not subtract the items' log sampling probabilities from the logits")
     ap.add_argument("--w2v_dim", type=int, default=None, help="w2v: vector width, a multiple of 4 in [4, 512] "
                                                               "(default 16 with --small, else 128)")
     ap.add_argument("--w2v_negatives", type=int, default=None, help="w2v: negatives per pair, 1..64 (default 5)")
@@ -255,9 +266,10 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm", "ffm", "gbdt"):
-        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm, ffm and gbdt, "
-                 f"not {args.model}")
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm", "ffm", "gbdt",
+                                                  "twotower"):
+        ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm, ffm, gbdt and "
+                 f"twotower, not {args.model}")
     gbdt_flags = [f"--{k}" for k in ("gbdt_depth", "gbdt_bins", "gbdt_lr", "gbdt_lambda", "gbdt_rows",
                                      "gbdt_features") if getattr(args, k) is not None]
     if args.gbdt_model_out:
@@ -420,6 +432,31 @@ def parse(argv=None):
             ap.error("--model als: no --eval_every (every sweep reports the held-out RMSE)")
     elif als_flags:
         ap.error(f"{' / '.join(als_flags)}: --model als only, not {args.model}")
+    tt_flags = [f"--{k}" for k in ("tt_dim", "tt_tau", "tt_users", "tt_items", "tt_no_bias_correction")
+                if getattr(args, k) is not None]
+    if args.model == "twotower":
+        args.tt_dim = (16 if args.small else 64) if args.tt_dim is None else args.tt_dim
+        args.tt_tau = 0.1 if args.tt_tau is None else args.tt_tau
+        args.tt_users = (256 if args.small else 65536) if args.tt_users is None else args.tt_users
+        args.tt_items = (128 if args.small else 16384) if args.tt_items is None else args.tt_items
+        if args.tt_dim % 4 or not 8 <= args.tt_dim <= 128:
+            ap.error(f"--model twotower: --tt_dim {args.tt_dim} must be a multiple of 4 in [8, 128]")
+        if not 0 < args.tt_tau < float("inf"):
+            ap.error(f"--model twotower: --tt_tau {args.tt_tau} must be positive and finite")
+        if args.tt_users < 1 or args.tt_items < 1:
+            ap.error("--model twotower: --tt_users and --tt_items must be >= 1")
+        if args.batch < 0 or args.batch >= 1 << 30:
+            ap.error(f"--model twotower: --batch {args.batch} pairs per clock must be in [1, 2^30) (0: the default)")
+        if args.input:
+            ap.error("--model twotower reads the synthetic pair stream only, not an --input file")
+        if args.transport == "onesided":
+            ap.error("--model twotower needs --transport collective (no twotower on the one-sided transport)")
+        if args.kStorageType != "vector":
+            ap.error("--model twotower needs --kStorageType Vector (no twotower on hash tables)")
+        if args.value_dtype != "float32":
+            ap.error(f"--model twotower keeps float32 rows, not --value_dtype {args.value_dtype}")
+    elif tt_flags:
+        ap.error(f"{' / '.join(tt_flags)}: --model twotower only, not {args.model}")
     gmm_flags = [f"--{k}" for k in ("gmm_rho0", "gmm_kappa", "gmm_var_floor", "gmm_covariance",
                                           "gmm_reg_covar") if getattr(args, k) is not None]
     if args.model == "gmm":
@@ -891,6 +928,18 @@ def build(args, comm):
             return torch.tensor([m.rmse(*hold)], device=dev)
 
         return m, {0: m.table}, (lambda: _Resident(None)), als_step, 1
+    if args.model == "twotower":
+        from .data.synthetic import PairSynth
+        from .models.twotower import TwoTower, TwoTowerConfig
+
+        B = args.batch or (128 if args.small else 8192)
+        m = TwoTower(TwoTowerConfig(users=args.tt_users, items=args.tt_items, dim=args.tt_dim, tau=args.tt_tau,
+                                    lr=args.alpha, correct_bias=not args.tt_no_bias_correction, seed=args.seed,
+                                    consistency=args.consistency, staleness=args.staleness), comm)
+        # one teacher for every rank (seed), this rank's own pair stream
+        synth = PairSynth(args.tt_users, args.tt_items, k_teacher=4, batch=B, seed=args.seed, zipf=1.0)
+        m.set_item_counts(synth.item_counts())
+        return m, {0: m.table}, (lambda: _Skippable(synth.holdout(seed + 1))), (lambda b: m.train_step(*b)), B
     if args.model == "gmm":
         from .models.gmm import GMM, GMMConfig
 
@@ -1202,6 +1251,13 @@ def main(argv=None):
             torch.cuda.synchronize(comm.device)
         dt = time.perf_counter() - t0
         t_eval += dt
+        if args.model == "twotower":  # the mean held-out in-batch loss: there is no AUC of a softmax over the batch
+            n = args.eval_batches * per_step * comm.world
+            evals.append([it_done, None, round(r, 6), n])
+            log.event("eval", step=it_done, logloss=r, n=n, eval_ms=round(dt * 1e3, 3))
+            if rank == 0:
+                print(f"Eval iteration={it_done} loss={r:.5f} n={n}", flush=True)
+            return
         evals.append([it_done, r["auc"], r["logloss"], r["n"]])
         log.event("eval", step=it_done, auc=r["auc"], auc_slack=r["auc_slack"], logloss=r["logloss"], n=r["n"],
                   n_pos=r["n_pos"], n_nan=r["n_nan"], eval_ms=round(dt * 1e3, 3))
@@ -1402,6 +1458,8 @@ def main(argv=None):
                           gmm_loglik=round(float(model.predict(args._gmm_hold)[1].double().mean()), 6))
         if model.full:
             ftrl_final.update(gmm_covariance="full")
+    if args.model == "twotower":
+        ftrl_final.update(tt_dim=model.d, tt_tau=model.cfg.tau)
     if args.model == "w2v":  # vectors() is a collective Get; the purity of the planted groups is read on the host
         ftrl_final.update(w2v_dim=model.d, w2v_pairs=model.total_pairs)
         if args._w2v_group:

@@ -19,7 +19,8 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         (a sweep of alternating least squares over 131072 users x 32768 Zipf items per rank, 64 ratings a user,
         clocks of --batch entities; --als_k; ms_per_step is ms per sweep), gmm (a clock of stepwise EM for a diagonal
         Gaussian mixture on --batch planted points; --gmm_K, --gmm_dims; --gmm_covariance full for full covariance
-        matrices on rotated planted points).
+        matrices on rotated planted points), twotower (a clock of two-tower retrieval with the in-batch softmax on
+        --batch pairs; --tt_dim, --tt_tau).
 """
 from __future__ import annotations
 
@@ -216,6 +217,29 @@ def build(args, comm):
         return m, step, B, "pairs/s", \
             dict(model=f"word2vec skip-gram, {args.w2v_negatives} negatives, {V} words, fp32 rows of {args.w2v_dim}, "
                        f"Zipf(1.05) words", seq_len=None)
+    if args.model == "twotower":
+        from minips_amd.models.twotower import TwoTower, TwoTowerConfig
+        from tools.bench_fm import draw_keys
+
+        # a clock on --batch pairs (default 8192): uniform users over 2^20 ids, Zipf(1.05) items over 2^18 ids, the
+        # bias correction from the same law's counts; a ring of ready pair batches
+        B, U, I = args.batch or 8192, 1 << 20, 1 << 18
+        gen = torch.Generator(device=dev).manual_seed(1000 + r)
+        m = TwoTower(TwoTowerConfig(users=U, items=I, dim=args.tt_dim, tau=args.tt_tau, consistency=args.consistency,
+                                    staleness=args.staleness), comm)
+        m.set_item_counts(torch.bincount(draw_keys("zipf", 1 << 24, I, 1.05, torch.Generator(device=dev).manual_seed(7),
+                                                   dev), minlength=I))
+        ring = [(torch.randint(0, U, (B,), device=dev, generator=gen), draw_keys("zipf", B, I, 1.05, gen, dev))
+                for _ in range(4)]
+        at = [0]
+
+        def step():
+            at[0] += 1
+            return m.train_step(*ring[at[0] % len(ring)])
+
+        return m, step, B, "pairs/s", \
+            dict(model=f"two-tower retrieval, in-batch softmax over {B} pairs, fp32 rows of {args.tt_dim}, tau "
+                       f"{args.tt_tau}, Zipf(1.05) items", seq_len=None)
     if args.model == "als":
         from minips_amd.data.synthetic import MFSynth
         from minips_amd.models.als import ALS, ALSConfig, transpose_csr
@@ -325,7 +349,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
                                                          "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
-                                                         "gbdt", "lda", "w2v", "als", "gmm"])
+                                                         "gbdt", "lda", "w2v", "als", "gmm", "twotower"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -370,6 +394,8 @@ def main():
     ap.add_argument("--w2v_negatives", "--w2v-negatives", dest="w2v_negatives", type=int, default=5,
                     help="w2v: negatives per pair")
     ap.add_argument("--als_k", "--als-k", dest="als_k", type=int, default=32, help="als: factors")
+    ap.add_argument("--tt_dim", "--tt-dim", dest="tt_dim", type=int, default=64, help="twotower: embedding width")
+    ap.add_argument("--tt_tau", "--tt-tau", dest="tt_tau", type=float, default=0.1, help="twotower: temperature")
     ap.add_argument("--gmm_K", "--gmm-K", dest="gmm_K", type=int, default=64, help="gmm: components")
     ap.add_argument("--gmm_dims", "--gmm-dims", dest="gmm_dims", type=int, default=64, help="gmm: dimensions")
     ap.add_argument("--gmm_covariance", "--gmm-covariance", dest="gmm_covariance", choices=["diag", "full"],
