@@ -36,6 +36,8 @@
   ``gmm_full_estep``): a fifteenth small torch extension, same rule.
 * ``_ibsk``     -- the in-batch sampled softmax kernels of the two-tower model (``ops.ibs_forward`` /
   ``ibs_backward``): a sixteenth small torch extension, same rule.
+* ``_kmk``      -- K-Means' fused step kernels (``ops.km_nearest`` / ``km_sums``): a seventeenth small torch
+  extension, same rule.
 """
 from __future__ import annotations
 
@@ -151,6 +153,11 @@ def ibsk():
     return _load("_ibsk", "gfx950 HIP in-batch sampled softmax kernels")
 
 
+def kmk():
+    """Return the HIP K-Means fused step kernel module or raise a loud error."""
+    return _load("_kmk", "gfx950 HIP K-Means fused step kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -218,6 +225,10 @@ def gmmfk_available() -> bool:
 
 def ibsk_available() -> bool:
     return _available(ibsk)
+
+
+def kmk_available() -> bool:
+    return _available(kmk)
 
 
 def native_dir() -> str:

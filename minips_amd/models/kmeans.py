@@ -32,6 +32,9 @@ class KMeansConfig:
     staleness: int = 0
     seed: int = 0
     init_mode: str = "random"  # random / kmeans++ / kmeans_parallel (used with init_data)
+    # classic: kmeans_assign + scatter_add_rows + bincount. fused: ops.km_step (csrc/kernels/kmeans.h) -- an fp32 MFMA
+    # sweep and an atomic-free group-by, the same bits on every run; dense points only, K <= 4096, dims <= 256
+    step: str = "classic"
 
 
 def _min_sqdist(X, C):
@@ -123,6 +126,14 @@ class KMeans:
                  init_data: torch.Tensor | None = None):
         self.cfg, self.comm = cfg, comm
         K, D = cfg.K, cfg.dims
+        if cfg.step not in ("classic", "fused"):
+            raise ValueError(f"kmeans: unknown step {cfg.step!r} (classic / fused)")
+        if cfg.step == "fused" and not ops.km_shape_ok(K, D):
+            raise ValueError(f"kmeans: step='fused' needs 1 <= K <= {ops.KM_MAX_K} and 1 <= dims <= {ops.KM_MAX_D}, "
+                             f"got K = {K}, dims = {D}")
+        # fused: the points without a centre (a non-finite feature, no live centre), counted on the device
+        self.bad = torch.zeros(1, dtype=torch.int32, device=comm.device) if cfg.step == "fused" else None
+        self.bad_total = 0  # ... as of the last drain()
         self.table = DenseTable(comm, K * D + K, optimizer="add", pull_dtype=torch.float32,
                                 consistency=cfg.consistency, staleness=cfg.staleness)
         full = torch.zeros(K * D + K)
@@ -145,12 +156,18 @@ class KMeans:
         P = self.table.get()
         C = P[: K * D].view(K, D)
         N = P[K * D: K * D + K]
-        dist = torch.empty(X.shape[0], dtype=torch.float32, device=dev)
-        assign = ops.kmeans_assign(X, C, dist=dist)
-        idx = assign.to(torch.int64)
-        sums = torch.zeros(K, D, dtype=torch.float32, device=dev)
-        ops.scatter_add_rows(X.contiguous(), idx, sums)
-        n = torch.bincount(idx, minlength=K).to(torch.float32)
+        if self.cfg.step == "fused":
+            _, _, sums, counts, sse = ops.km_step(X, C, bad=self.bad)
+            n = counts.to(torch.float32)
+            loss = sse[0]
+        else:
+            dist = torch.empty(X.shape[0], dtype=torch.float32, device=dev)
+            assign = ops.kmeans_assign(X, C, dist=dist)
+            idx = assign.to(torch.int64)
+            sums = torch.zeros(K, D, dtype=torch.float32, device=dev)
+            ops.scatter_add_rows(X.contiguous(), idx, sums)
+            n = torch.bincount(idx, minlength=K).to(torch.float32)
+            loss = None
         n_glob = self.comm.all_reduce_(n.clone())
         denom = (N + n_glob).clamp_min(1.0)
         G = self.table.grad
@@ -158,12 +175,14 @@ class KMeans:
         G[K * D: K * D + K].copy_(n)
         self.table.add()
         self.table.clock()
-        return dist.sum()
+        return dist.sum() if loss is None else loss
 
     def train_step_csr(self, rowptr, cols, vals):
         """Sparse points (CSR batch; the reference clusters libsvm rows, kmeans_helper.hpp:45-66,
         kmeans.cpp:238-267) against the dense centres: the same batched 1/count update as
         train_step. Returns the batch's summed squared distance (before the update)."""
+        if self.cfg.step == "fused":
+            raise ValueError("kmeans: step='fused' takes dense points (train_step), not CSR batches")
         K, D = self.cfg.K, self.cfg.dims
         dev = self.comm.device
         P = self.table.get()
@@ -186,3 +205,6 @@ class KMeans:
 
     def drain(self):
         self.table.drain()
+        if self.bad is not None:
+            self.bad_total += int(self.bad.item())
+            self.bad.zero_()

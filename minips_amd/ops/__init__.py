@@ -13,8 +13,8 @@ import math
 
 import torch
 
-from .._native import (alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, ldak, optk, w2vk,
-                       wdftrlk)
+from .._native import (alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, kmk, ldak, optk,
+                       w2vk, wdftrlk)
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -2519,6 +2519,86 @@ def kmeans_assign(X, C, assign=None, dist=None, mfma=None):
     if dist is not None:
         dist.copy_(best.to(dist.dtype))
     return assign
+
+
+# ----------------------------------------------------------------------------- K-Means: the fused step
+KM_MAX_K, KM_MAX_D, KM_CHUNK, KM_WAVE_MAX = 4096, 256, 64, 512  # csrc/kernels/kmeans.h (the binding exports them too)
+
+
+def km_shape_ok(K: int, D: int) -> bool:
+    return 1 <= K <= KM_MAX_K and 1 <= D <= KM_MAX_D
+
+
+def _km_check(op, X, K, D):
+    if X.dim() != 2 or X.dtype != torch.float32 or X.shape[1] != D:
+        raise ValueError(f"kmeans: {op} takes fp32 points [n, {D}], got {X.dtype} {tuple(X.shape)}")
+    if not km_shape_ok(K, D):
+        raise ValueError(f"kmeans: {op}: K = {K}, D = {D}, expected 1 <= K <= {KM_MAX_K} and 1 <= D <= {KM_MAX_D}")
+
+
+def km_nearest(X, C, bad=None, blocks=0):
+    """The nearest centre of every point of X fp32 [n, D] (row stride >= D, any alignment) among C fp32 [K, D] (the
+    rule: csrc/kernels/kmeans.h): cn_k = |c_k|^2, t_ik = cn_k - 2 <x_i, c_k>, assign_i = argmin_k t_ik over the centres
+    with a finite cn (the lowest index on ties), dist_i = |x_i - c_assign|^2 from the winner's row, sse = sum_i dist_i
+    in fp64. Returns (assign int32 [n], dist fp32 [n], sse fp64 [1], bad int32 [1]). A point whose |x|^2 is not finite
+    or that finds no live centre gets assign -1 and dist NaN, adds nothing to sse and 1 to ``bad`` (a counter that is
+    added to when given). On the GPU a fused gfx950 sweep (fp32 MFMA, no score matrix, no float atomics, the same bits
+    on every run and for every grid size ``blocks``); the CPU path is the fp64 PyTorch reference of the rule."""
+    if C.dim() != 2 or C.dtype != torch.float32:
+        raise ValueError(f"kmeans: km_nearest takes fp32 centres [K, D], got {C.dtype} {tuple(C.shape)}")
+    K, D = C.shape
+    _km_check("km_nearest", X, K, D)
+    n, dev = X.shape[0], X.device
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if _gpu(X):
+        assign = torch.empty(n, dtype=torch.int32, device=dev)
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        sse = torch.empty(1, dtype=torch.float64, device=dev)
+        kmk().km_nearest(X, C.contiguous(), assign, dist, sse, bad, int(blocks))
+        return assign, dist, sse, bad
+    live = torch.isfinite((C * C).sum(1))
+    ok = torch.isfinite((X * X).sum(1)) & bool(live.any())
+    d = torch.cdist(torch.where(ok[:, None], X, torch.zeros(())).double(),
+                    torch.where(live[:, None], C, torch.zeros(())).double()) ** 2
+    d = torch.where(live, d, torch.full((), float("inf"), dtype=torch.float64))
+    best = d.min(1).values
+    first = torch.where(d == best[:, None], torch.arange(K), torch.full((), K)).min(1).values  # the lowest index
+    assign = torch.where(ok, first, torch.full((), -1)).to(torch.int32)
+    dist = torch.where(ok, best, torch.full((), float("nan"), dtype=torch.float64)).float()
+    sse = torch.where(ok, dist, torch.zeros(())).double().sum().reshape(1)
+    bad += int((~ok).sum())
+    return assign, dist, sse, bad
+
+
+def km_sums(X, assign, K, blocks=0):
+    """Per-centre sums and counts of the points X fp32 [n, D] under assign int32 [n] (csrc/kernels/kmeans.h): sums fp32
+    [K, D], sums[k] = the x_i with assign_i == k added in ascending i, counts int32 [K]; an assign outside [0, K)
+    contributes nothing, an empty centre gets zeros. On the GPU an integer group-by (members sorted by centre, then
+    point) and the atomic-free row reduce: no float atomics, no sort or bincount, the same bits on every run and for
+    every grid size; the CPU path is index_add_ / bincount."""
+    D = X.shape[1] if X.dim() == 2 else 0
+    _km_check("km_sums", X, int(K), D)
+    n, dev = X.shape[0], X.device
+    if assign.dtype != torch.int32 or tuple(assign.shape) != (n,):
+        raise ValueError(f"kmeans: km_sums takes assign int32 [{n}], got {assign.dtype} {tuple(assign.shape)}")
+    if _gpu(X):
+        sums = torch.empty(K, D, dtype=torch.float32, device=dev)
+        counts = torch.empty(K, dtype=torch.int32, device=dev)
+        kmk().km_sums(X, assign, sums, counts, int(blocks))
+        return sums, counts
+    idx = assign.to(torch.int64)
+    keep = (idx >= 0) & (idx < K)
+    sums = torch.zeros(K, D, dtype=torch.float32).index_add_(0, idx[keep], X[keep])
+    return sums, torch.bincount(idx[keep], minlength=K).to(torch.int32)
+
+
+def km_step(X, C, bad=None, blocks=0):
+    """One K-Means step's statistics: km_nearest, then km_sums under its assignment. Returns (assign, dist, sums,
+    counts, sse); ``bad`` as in km_nearest."""
+    assign, dist, sse, _ = km_nearest(X, C, bad=bad, blocks=blocks)
+    sums, counts = km_sums(X, assign, C.shape[0], blocks=blocks)
+    return assign, dist, sums, counts, sse
 
 
 # ----------------------------------------------------------------------------- dense models

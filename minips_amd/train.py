@@ -119,6 +119,9 @@ def parse(argv=None):
     ap.add_argument("--kmeans_init_mode", default="", choices=["", "random", "kmeans++", "kmeans_parallel"],
                     help="K-Means seeding from a batch of local data (reference kmeans.cpp:154-192); "
                          "empty: N(0,1) centres")
+    ap.add_argument("--kmeans_step", choices=["classic", "fused"], default=None,
+                    help="kmeans: classic (kmeans_assign + scatter-add, the default) or fused (the fp32 MFMA sweep and "
+                         "the atomic-free centre sums of ops.km_step; dense points, K <= 4096)")
     ap.add_argument("--report_prefix", default="")
     ap.add_argument("--report_interval", type=int, default=10)
     ap.add_argument("--metrics_dir", default="")
@@ -498,6 +501,13 @@ def parse(argv=None):
             ap.error("--model gmm: no --eval_every (the final JSON reports the held-out log-likelihood)")
     elif gmm_flags:
         ap.error(f"{' / '.join(gmm_flags)}: --model gmm only, not {args.model}")
+    if args.kmeans_step is not None:
+        if args.model != "kmeans":
+            ap.error(f"--kmeans_step: --model kmeans only, not {args.model}")
+        if args.input:
+            ap.error("--kmeans_step chooses the dense step: not with --input (the CSR path)")
+        if args.kmeans_step == "fused" and not 0 <= args.K <= 4096:
+            ap.error(f"--kmeans_step fused: --K {args.K} must lie in [1, 4096]")
     if args.model == "fm":
         if args.fm_k % 4 or not 4 <= args.fm_k <= 60:
             ap.error(f"--model fm: --fm_k {args.fm_k} must be a multiple of 4 in [4, 60]")
@@ -1010,7 +1020,7 @@ def build(args, comm):
 
         cfg = KMeansConfig(K=args.K or (8 if args.small else 1000), dims=16 if args.small else 128,
                            consistency=args.consistency, staleness=args.staleness,
-                           init_mode=args.kmeans_init_mode or "random", seed=seed)
+                           init_mode=args.kmeans_init_mode or "random", seed=seed, step=args.kmeans_step or "classic")
         B = args.batch or (256 if args.small else 65536)
         # seeding reads its own batch of local data (rank 0's seeds are broadcast)
         init = _GaussData(max(B, cfg.K), cfg.dims, dev, seed + 7919).next() if args.kmeans_init_mode else None
@@ -1458,6 +1468,8 @@ def main(argv=None):
                           gmm_loglik=round(float(model.predict(args._gmm_hold)[1].double().mean()), 6))
         if model.full:
             ftrl_final.update(gmm_covariance="full")
+    if args.model == "kmeans" and args.kmeans_step == "fused":
+        ftrl_final.update(kmeans_step="fused")
     if args.model == "twotower":
         ftrl_final.update(tt_dim=model.d, tt_tau=model.cfg.tau)
     if args.model == "w2v":  # vectors() is a collective Get; the purity of the planted groups is read on the host

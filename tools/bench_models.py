@@ -275,12 +275,14 @@ def build(args, comm):
         from minips_amd.models.kmeans import KMeans, KMeansConfig
 
         B = args.batch or 65536
-        cfg = KMeansConfig(K=1000, dims=128, consistency=args.consistency, staleness=args.staleness)
+        cfg = KMeansConfig(K=1000, dims=128, consistency=args.consistency, staleness=args.staleness,
+                           step=args.kmeans_step or "classic")
         m = KMeans(cfg, comm)
         g = torch.Generator(device=dev)
         g.manual_seed(r)
         return m, (lambda: m.train_step(torch.randn(B, cfg.dims, generator=g, device=dev))), B, "samples/s", \
-            dict(model="mini-batch K-Means K=1000 D=128", seq_len=None)
+            dict(model="mini-batch K-Means K=1000 D=128", seq_len=None,
+                 **({"kmeans_step": "fused"} if args.kmeans_step == "fused" else {}))
     if args.model in ("widedeep", "widedeep-ssp", "deepfm", "dcn"):
         from minips_amd.data.synthetic import CriteoSynth
         from minips_amd.models.widedeep import WideDeep, WideDeepConfig
@@ -402,7 +404,11 @@ def main():
                     default="diag", help="gmm: diagonal or full covariance matrices")
     ap.add_argument("--gbdt_features", "--gbdt-features", dest="gbdt_features", type=int, default=32,
                     help="gbdt: features (the teacher reads 5)")
+    ap.add_argument("--kmeans_step", "--kmeans-step", dest="kmeans_step", choices=["classic", "fused"], default=None,
+                    help="kmeans: the classic composition (default) or the fused step (ops.km_step)")
     args = ap.parse_args()
+    if args.kmeans_step is not None and args.model != "kmeans":
+        ap.error(f"--kmeans_step: --model kmeans only, not {args.model}")
     if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "fm", "ffm"):
         ap.error("--wide_optimizer ftrl: --model widedeep, deepfm, dcn, fm and ffm only")
     if args.model == "dcn" and not 1 <= args.cross_layers <= 4:
