@@ -38,6 +38,8 @@
   ``ibs_backward``): a sixteenth small torch extension, same rule.
 * ``_kmk``      -- K-Means' fused step kernels (``ops.km_nearest`` / ``km_sums``): a seventeenth small torch
   extension, same rule.
+* ``_cink``     -- xDeepFM's Compressed Interaction Network layers over the assembled Wide & Deep input
+  (``ops.wd_cin_forward`` / ``wd_cin_backward``): an eighteenth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -158,6 +160,11 @@ def kmk():
     return _load("_kmk", "gfx950 HIP K-Means fused step kernels")
 
 
+def cink():
+    """Return the HIP Compressed Interaction Network kernel module or raise a loud error."""
+    return _load("_cink", "gfx950 HIP Compressed Interaction Network kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -229,6 +236,10 @@ def ibsk_available() -> bool:
 
 def kmk_available() -> bool:
     return _available(kmk)
+
+
+def cink_available() -> bool:
+    return _available(cink)
 
 
 def native_dir() -> str:

@@ -83,6 +83,13 @@ class WideDeepConfig:
     # dense layout's entry "cross" directly behind W1, trained by the dense Adam. Collective transport only,
     # 1 <= L <= 4, emb_dim in [1, 64], d <= ops.CROSS_MAX_D. 0: the layout and the step are Wide&Deep's.
     cross_layers: int = 0
+    # xDeepFM (Lian et al., 2018): cin_layers = (H_1, ..., H_T) feature-map counts of a Compressed Interaction Network
+    # over the F field embeddings -- X^k[h] = sum_{i, j} W^k[h, i, j] (X^{k-1}[i] o X^0[j]), explicit vector-wise
+    # crosses of degree k + 1 -- whose sum-pooled maps enter the wide logit through w_out (ops.wd_cin_forward where the
+    # cross layers run, ops.wd_cin_backward behind them; the rule: csrc/kernels/cin.h). The parameters W^1 | ... | W^T |
+    # w_out are the dense layout's entry "cin" behind W1 (and "cross"), trained by the dense Adam. Collective
+    # transport only, 1 <= T <= 3, H_k % 16 == 0 in [16, 128], F <= 64, emb_dim % 8 == 0 in [8, 64]. (): Wide&Deep's.
+    cin_layers: tuple = ()
 
     def __post_init__(self):
         if self.transport == "auto":
@@ -112,6 +119,17 @@ class WideDeepConfig:
             if d > ops.CROSS_MAX_D:
                 raise ValueError(f"cross_layers: the input has d = {d} columns, the kernels take d <= "
                                  f"{ops.CROSS_MAX_D}")
+        if not isinstance(self.cin_layers, (tuple, list)):
+            raise ValueError(f"cin_layers is {self.cin_layers!r}, expected a tuple of feature-map counts")
+        self.cin_layers = tuple(self.cin_layers)
+        if self.cin_layers:
+            if "onesided" in (self.transport, self.dense_transport):
+                raise ValueError("cin_layers needs transport 'collective' (the CIN layers are not built for the "
+                                 "one-sided transport)")
+            try:
+                ops.wd_cin_check(self.F, self.emb_dim, self.cin_layers)
+            except RuntimeError as e:
+                raise ValueError(f"cin_layers: {e}") from None
 
     @property
     def F(self):
@@ -250,6 +268,12 @@ class WideDeep(LookaheadPlans):
                 # cross gradient (written after the dX dgrad) exists
                 self.layout["cross"] = (off, (2 * cfg.cross_layers + 1, _align(self.k_in[0])))
                 off += _align((2 * cfg.cross_layers + 1) * _align(self.k_in[0]), 64)
+            if i == 0 and cfg.cin_layers:
+                # the CIN parameters W^1 | ... | W^T | w_out (ops.wd_cin_layout, each part 64-aligned), behind W1 and
+                # "cross": inside layer 1's bucket for the same reason -- their gradient exists after the dX dgrad
+                n_cin = ops.wd_cin_layout(cfg.F, cfg.cin_layers)[1]
+                self.layout["cin"] = (off, (n_cin,))
+                off += n_cin
             if i > 0:
                 self.layout[f"b{i + 1}"] = (off, (n_out,))
                 off += _align(n_out, 64)
@@ -281,6 +305,12 @@ class WideDeep(LookaheadPlans):
         if self.cfg.cross_layers:  # drawn after the existing parameters: those keep their values; b_l = 0
             d = self.k_in[0]
             ops.kaiming_uniform_(self.view(full, "cross")[0::2, :d], d, g)
+        if self.cfg.cin_layers:  # drawn last, the cross parameters included: every earlier value stays; the pad is 0
+            F = self.cfg.F
+            Ws, w_out = ops.wd_cin_views(self.view(full, "cin"), F, self.cfg.cin_layers)
+            for W in Ws:
+                ops.kaiming_uniform_(W[:, :, :F], W.shape[1] * F, g)
+            ops.kaiming_uniform_(w_out, w_out.numel(), g)
         return full.to(dev)
 
     def view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
@@ -323,6 +353,8 @@ class WideDeep(LookaheadPlans):
                 self._bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
             if cfg.cross_layers:  # the cross layers' dot products and constants, and the partial batch sums
                 self._bufs[B].update(self._cross_buffers(B, part=True))
+            if cfg.cin_layers:  # the feature maps, their gradients and the per-chunk partial weight gradients
+                self._bufs[B]["cin"] = ops.wd_cin_buffers(B, cfg.F, cfg.emb_dim, cfg.cin_layers, dev)
         return self._bufs[B]
 
     def _cross_buffers(self, B, part=False):
@@ -337,6 +369,11 @@ class WideDeep(LookaheadPlans):
         """wide += the cross layers' output over the assembled X (after the DeepFM term, before the head)."""
         ops.wd_cross_forward(b["X"], self.k_in[0], self.view(P, "cross"), self.cfg.cross_layers, b["wide"], b["p"],
                              b["k"])
+
+    def _cin_forward(self, b, P):
+        """wide += the CIN term over the assembled X (where the cross layers run: it reads the pulled values)."""
+        cfg = self.cfg
+        ops.wd_cin_forward(b["X"], cfg.F, cfg.emb_dim, self.view(P, "cin"), cfg.cin_layers, b["wide"], b["cin"])
 
     def _forward(self, b, P):
         ops.linear_fwd(b["X"], self.view(P, "W1"), None, "relu", out=b["H1"])
@@ -357,6 +394,8 @@ class WideDeep(LookaheadPlans):
             ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
         if self.cfg.cross_layers:
             self._cross_forward(b, P)
+        if self.cfg.cin_layers:
+            self._cin_forward(b, P)
         self._forward(b, P)
         h = self.cfg.hidden[-1]
         w4 = self.view(P, "w4").float()
@@ -377,6 +416,8 @@ class WideDeep(LookaheadPlans):
                 bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
             if cfg.cross_layers:
                 bufs[B].update(self._cross_buffers(B))
+            if cfg.cin_layers:
+                bufs[B]["cin"] = ops.wd_cin_buffers(B, cfg.F, cfg.emb_dim, cfg.cin_layers, dev, train=False)
         return bufs[B]
 
     def evaluate(self, batches, evaluator=None) -> dict:
@@ -409,6 +450,8 @@ class WideDeep(LookaheadPlans):
                 ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
             if cfg.cross_layers:
                 self._cross_forward(b, P)
+            if cfg.cin_layers:
+                self._cin_forward(b, P)
             self._forward(b, P)
             ev.update_head(b["H3"], w4[:h], w4[h:h + 1], b["wide"], labels)
         ev.reduce(self.comm)
@@ -471,6 +514,8 @@ class WideDeep(LookaheadPlans):
         w4, gw4 = self.view(P, "w4"), self.view(G, "w4")
         if cfg.cross_layers:  # DCN: wide += <x_L, w_c>; it reads the pulled values, so behind the Adam wait above
             self._cross_forward(b, P)
+        if cfg.cin_layers:  # xDeepFM: wide += <w_out, pooled CIN maps>; the pulled values again
+            self._cin_forward(b, P)
         sink = self.dense.slab_sink() if hasattr(self.dense, "slab_sink") else None
         side = self._side
         defer = _HEAD_DEFER and side.stream is not None
@@ -511,7 +556,7 @@ class WideDeep(LookaheadPlans):
             ops.linear_dgrad(b["dH1"], self.view(P, "W1"), n_cols=F * D, out=b["dX"])
         # W's last reader of the step is issued: a side-stream dense Adam may start after this point
         adam_point = _ADAM_AFTER_DGRAD and self.comm.world == 1
-        w_read = side.point() if adam_point and not cfg.cross_layers else None
+        w_read = side.point() if adam_point and not cfg.cross_layers and not cfg.cin_layers else None
         if cfg.fm_term:  # DeepFM: dX += dz (S - v) per lookup, in the order the dgrad wrote the rows
             ops.wd_fm_backward(b["X"], b["S"], b["dwide"], b["dX"], F, D, perm=plan.csr[2] if sorted_rows else None)
         if cfg.cross_layers:
@@ -523,6 +568,13 @@ class WideDeep(LookaheadPlans):
             # the side-stream Adam rewrites the pulled values and clears G: the cross backward still reads the
             # former and the fold writes the latter, so here the point the Adam waits for lies behind the fold, not
             # behind the dX dgrad (DeepFM's term touches neither and may stay behind the point)
+            w_read = side.point() if adam_point else None
+        if cfg.cin_layers:
+            # xDeepFM: per layer T .. 1 the weight gradient (partials, folded into G) and the data backward; layer 1
+            # adds the embedding gradient to dX. It reads the pulled values and writes G like the cross backward, so
+            # the point the side-stream Adam waits for lies behind its last fold as well
+            ops.wd_cin_backward(b["X"], F, D, self.view(P, "cin"), cfg.cin_layers, b["dwide"], b["dX"], b["cin"],
+                                self.view(G, "cin"), perm=plan.csr[2] if sorted_rows else None)
             w_read = side.point() if adam_point else None
         if _W1_LATE:  # the layer-1 weight gradient beside the memory-bound embedding backward instead
             with side.fork():

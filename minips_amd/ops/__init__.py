@@ -13,8 +13,8 @@ import math
 
 import torch
 
-from .._native import (alsk, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, kmk, ldak, optk,
-                       w2vk, wdftrlk)
+from .._native import (alsk, cink, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, kmk, ldak,
+                       optk, w2vk, wdftrlk)
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -917,6 +917,242 @@ def wd_cross_fold(part, Pc, d, L, Gc):
         t = Sd[l] * W[l]
         r = r + t
     return Gc
+
+
+# ----------------------------------------------------------------------------- xDeepFM's CIN layers
+CIN_MAX_T = 3        # csrc/kernels/cin.h: kCinMaxT, kCinMaxH, kCinMaxM, kCinMaxD, kCinChunk, kCinMaxChunks
+CIN_MAX_H = 128
+CIN_MAX_F = 64
+CIN_MAX_D = 64
+CIN_CHUNK = 256
+CIN_MAX_CHUNKS = 64
+
+
+def wd_cin_check(F, D, layers):
+    """The shapes of csrc/kernels/cin.h's rule, or a RuntimeError naming what is outside it."""
+    layers = tuple(layers)
+    if not 1 <= len(layers) <= CIN_MAX_T or any(isinstance(h, bool) or not isinstance(h, int) or h % 16
+                                                 or not 16 <= h <= CIN_MAX_H for h in layers):
+        raise RuntimeError(f"wd_cin: layers is {layers!r}, expected 1 .. {CIN_MAX_T} multiples of 16 in "
+                           f"[16, {CIN_MAX_H}]")
+    if not 1 <= F <= CIN_MAX_F:
+        raise RuntimeError(f"wd_cin: F is {F}, expected 1 <= F <= {CIN_MAX_F}")
+    if D % 8 or not 8 <= D <= CIN_MAX_D:
+        raise RuntimeError(f"wd_cin: D is {D}, expected a multiple of 8 in [8, {CIN_MAX_D}]")
+    return layers
+
+
+def wd_cin_chunk(B):
+    """Samples per partial of the batch sums: a function of B alone (cin.h's cin_chunk)."""
+    B = int(B)
+    return CIN_CHUNK if B <= CIN_CHUNK * CIN_MAX_CHUNKS else (-(-B // CIN_MAX_CHUNKS) + 7) // 8 * 8
+
+
+def wd_cin_nchunks(B):
+    return -(-int(B) // wd_cin_chunk(B))
+
+
+def wd_cin_layout(F, layers):
+    """The flat parameter block W^1 | ... | W^T | w_out, each part 64-aligned: ([(offset, shape)] in that order,
+    total). W^k is [H_k, H_{k-1}, align8(F)] with H_0 = F; w_out is [sum(layers)]."""
+    mp, hp, off, parts = (F + 7) // 8 * 8, F, 0, []
+    for h in layers:
+        parts.append((off, (h, hp, mp)))
+        off += (h * hp * mp + 63) // 64 * 64
+        hp = h
+    parts.append((off, (sum(layers),)))
+    return parts, off + (sum(layers) + 63) // 64 * 64
+
+
+def wd_cin_views(flat, F, layers):
+    """([W^1 .. W^T], w_out) as views of a flat block laid out by wd_cin_layout."""
+    parts, _ = wd_cin_layout(F, layers)
+    views = [flat[o: o + math.prod(s)].view(s) for o, s in parts]
+    return views[:-1], views[-1]
+
+
+def wd_cin_buffers(B, F, D, layers, device, train=True):
+    """The CIN buffers of a batch size: XK bf16 [B, Hs, D] (every layer's feature maps) and p fp32 [B, Hs]; for
+    training also dXK, the fp32 embedding-gradient workspace g0 [B, F, D] and the per-chunk partials -- ``part``
+    is sized for the largest layer and reused layer by layer (each fold runs before the next weight gradient), so
+    the workspace is at most CIN_MAX_CHUNKS copies of the largest W^k."""
+    hs, mp = sum(layers), (F + 7) // 8 * 8
+    bufs = dict(XK=torch.zeros(B, hs, D, dtype=torch.bfloat16, device=device),
+                p=torch.empty(B, hs, dtype=torch.float32, device=device))
+    if train:
+        nch = wd_cin_nchunks(B)
+        big = max(h * hp * mp for h, hp in zip(layers, (F,) + tuple(layers)))
+        bufs.update(dXK=torch.zeros(B, hs, D, dtype=torch.bfloat16, device=device),
+                    g0=torch.empty(B, F, D, dtype=torch.float32, device=device),
+                    part=torch.empty(nch * big, dtype=torch.float32, device=device),
+                    part_o=torch.empty(nch, hs, dtype=torch.float32, device=device))
+    return bufs
+
+
+def _cin_layer(F, layers, k):
+    """(H_{k-1}, H_k, o_{k-1}, o_k) of layer k (1-based)."""
+    off = sum(layers[: k - 1])
+    hp = F if k == 1 else layers[k - 2]
+    return hp, layers[k - 1], off - hp if k > 1 else 0, off
+
+
+def _cin_inputs(X, F, D, layers, k, XK):
+    hp, h, op, off = _cin_layer(F, layers, k)
+    x0 = X[:, : F * D].float().view(-1, F, D)
+    return x0, (x0 if k == 1 else XK[:, op: op + hp].float()), hp, h, op, off
+
+
+def _cin_z(xp, x0):
+    """z = bf16_rne(X^{k-1}[i, c] X^0[j, c]) as fp32 [B, Hp, F, D]."""
+    return (xp[:, :, None, :] * x0[:, None, :, :]).to(torch.bfloat16).float()
+
+
+def wd_cin_layer_forward(X, F, D, W, layers, k, XK, blocks=0):
+    """One CIN layer (the rule: csrc/kernels/cin.h): X^k[h, c] = bf16(sum_{i, j} W^k[h, i, j] z_{ij, c}) with
+    z = bf16(X^{k-1}[i, c] X^0[j, c]), read from and written to the stacked feature maps XK bf16 [B, sum(layers), D].
+    One gfx950 MFMA launch on the GPU (Z exists only in registers); the CPU path is the fp32 reference of the rule."""
+    F, D, k, layers = int(F), int(D), int(k), tuple(int(h) for h in layers)
+    if _gpu(X):
+        cink().wd_cin_layer_forward(X, F, D, W, list(layers), k, XK, int(blocks))
+        return XK
+    wd_cin_check(F, D, layers)
+    x0, xp, hp, h, _, off = _cin_inputs(X, F, D, layers, k, XK)
+    if tuple(W.shape) != (h, hp, (F + 7) // 8 * 8) or tuple(XK.shape) != (X.shape[0], sum(layers), D):
+        raise RuntimeError(f"wd_cin_layer_forward: W {tuple(W.shape)} / XK {tuple(XK.shape)} do not fit layer {k}")
+    acc = torch.einsum("hij,bijc->bhc", W[:, :, :F].float(), _cin_z(xp, x0))
+    XK[:, off: off + h] = acc.to(torch.bfloat16)
+    return XK
+
+
+def wd_cin_output(XK, w_out, wide, p, blocks=0):
+    """p[b, o] = sum_c float(XK[b, o, c]) and wide[b] += sum_o float(w_out[o]) p[b, o] (in place)."""
+    if _gpu(XK):
+        cink().wd_cin_output(XK, w_out, wide, p, int(blocks))
+        return p
+    p.copy_(XK.float().sum(2))
+    wide += p @ w_out.float()
+    return p
+
+
+def _cin_dxk(layers, k, h, off, dXK, w_out, dwide, D):
+    if k == len(layers):  # dX^T = bf16(dz w_out): the MFMA operand's rounding
+        return (dwide[:, None] * w_out[off: off + h].float()).to(torch.bfloat16).float()[:, :, None].expand(-1, -1, D)
+    return dXK[:, off: off + h].float()
+
+
+def wd_cin_layer_backward(X, F, D, W, layers, k, XK, dXK, w_out, dwide, g0, dX, perm=None, blocks=0):
+    """One layer of the CIN backward (csrc/kernels/cin.h): dZ = W^k^T dX^k is contracted at once into dX^{k-1}
+    (stored bf16 in dXK, k > 1) and into the running embedding gradient g0 fp32 [B, F, D]; layer 1 applies it: row
+    perm[b F + j] (b F + j without perm) of dX becomes bf16(float(dX) + g0[b, j]); out-of-range perm entries are
+    skipped. Call for k = T .. 1. In place."""
+    F, D, k, layers = int(F), int(D), int(k), tuple(int(h) for h in layers)
+    if _gpu(X):
+        cink().wd_cin_layer_backward(X, F, D, W, list(layers), k, XK, dXK, w_out, dwide, g0, perm, dX, int(blocks))
+        return dX
+    wd_cin_check(F, D, layers)
+    x0, xp, hp, h, op, off = _cin_inputs(X, F, D, layers, k, XK)
+    B = X.shape[0]
+    if dX.numel() != B * F * D or not dX.is_contiguous():
+        raise RuntimeError(f"wd_cin_layer_backward: dX {tuple(dX.shape)}, expected {B * F * D} contiguous elements")
+    dxk = _cin_dxk(layers, k, h, off, dXK, w_out, dwide, D)
+    dZ = torch.einsum("hij,bhc->bijc", W[:, :, :F].float(), dxk)
+    dxp = (dZ * x0[:, None]).sum(2)
+    g = (dZ * xp[:, :, None]).sum(1)
+    if k == 1:
+        g = g + dxp
+    else:
+        direct = dwide[:, None] * w_out[op: op + hp].float()
+        dXK[:, op: op + hp] = (dxp + direct[:, :, None]).to(torch.bfloat16)
+    if k < len(layers):
+        g = g + g0
+    if k > 1:
+        g0.copy_(g)
+        return dX
+    n = B * F
+    dx, g = dX.view(n, D), g.reshape(n, D)
+    if perm is None:
+        dx.copy_((dx.float() + g).to(torch.bfloat16))
+    else:
+        r = perm.long()
+        ok = (r >= 0) & (r < n)
+        r = r[ok]
+        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
+    return dX
+
+
+def wd_cin_layer_wgrad(X, F, D, layers, k, XK, dXK, w_out, dwide, part):
+    """Per-chunk partials of dW^k[h, i, j] = sum_b sum_c dX^k[h, c] z[(i, j), c] into part fp32 [nchunks, H_k,
+    H_{k-1} align8(F)] (written; the pad columns get zero). Before layer k's wd_cin_layer_backward for k < T."""
+    F, D, k, layers = int(F), int(D), int(k), tuple(int(h) for h in layers)
+    if _gpu(X):
+        cink().wd_cin_layer_wgrad(X, F, D, list(layers), k, XK, dXK, w_out, dwide, part)
+        return part
+    wd_cin_check(F, D, layers)
+    x0, xp, hp, h, _, off = _cin_inputs(X, F, D, layers, k, XK)
+    B, mp, ch = X.shape[0], (F + 7) // 8 * 8, wd_cin_chunk(X.shape[0])
+    if tuple(part.shape) != (wd_cin_nchunks(B), h, hp * mp):
+        raise RuntimeError(f"wd_cin_layer_wgrad: part {tuple(part.shape)}, expected "
+                           f"{(wd_cin_nchunks(B), h, hp * mp)}")
+    dxk, z = _cin_dxk(layers, k, h, off, dXK, w_out, dwide, D), _cin_z(xp, x0)
+    part.zero_()
+    for c in range(part.shape[0]):
+        s = slice(c * ch, (c + 1) * ch)
+        part[c].view(h, hp, mp)[:, :, :F] = torch.einsum("bhc,bijc->hij", dxk[s], z[s])
+    return part
+
+
+def wd_cin_wout_partial(dwide, p, part):
+    """part[chunk, o] = sum over the chunk's samples of dwide[b] p[b, o] (written)."""
+    if _gpu(p):
+        cink().wd_cin_wout_partial(dwide, p, part)
+        return part
+    ch = wd_cin_chunk(p.shape[0])
+    for c in range(part.shape[0]):
+        part[c] = dwide[c * ch: (c + 1) * ch] @ p[c * ch: (c + 1) * ch]
+    return part
+
+
+def wd_cin_fold(part, G):
+    """G += the chunks of ``part`` added in chunk order (fp32; G has the shape of one chunk)."""
+    if _gpu(part):
+        cink().wd_cin_fold(part, G)
+        return G
+    s = torch.zeros_like(G)
+    for c in range(part.shape[0]):
+        s = s + part[c].view(G.shape)
+    G += s
+    return G
+
+
+def wd_cin_forward(X, F, D, Pc, layers, wide, bufs, blocks=0):
+    """The CIN term of xDeepFM over the assembled input: every layer, then wide += <w_out, sum-pooled feature maps>.
+    Pc is the flat bf16 parameter block (wd_cin_layout), bufs come from wd_cin_buffers."""
+    layers = tuple(int(h) for h in layers)
+    Ws, w_out = wd_cin_views(Pc, F, layers)
+    for k in range(1, len(layers) + 1):
+        wd_cin_layer_forward(X, F, D, Ws[k - 1], layers, k, bufs["XK"], blocks)
+    wd_cin_output(bufs["XK"], w_out, wide, bufs["p"], blocks)
+    return bufs["p"]
+
+
+def wd_cin_backward(X, F, D, Pc, layers, dwide, dX, bufs, Gc, perm=None, blocks=0):
+    """The CIN backward from dwide: for k = T .. 1 the layer's weight gradient (per-chunk partials, folded in chunk
+    order and ADDED into the fp32 gradient block Gc laid out like Pc) and its data backward; the embedding gradient
+    is added to dX once, by layer 1; dw_out likewise from per-chunk partials."""
+    layers = tuple(int(h) for h in layers)
+    Ws, w_out = wd_cin_views(Pc, F, layers)
+    Gs, g_out = wd_cin_views(Gc, F, layers)
+    nch = wd_cin_nchunks(X.shape[0])
+    for k in range(len(layers), 0, -1):
+        W = Ws[k - 1]
+        part = bufs["part"][: nch * W.numel()].view(nch, W.shape[0], W.shape[1] * W.shape[2])
+        wd_cin_layer_wgrad(X, F, D, layers, k, bufs["XK"], bufs["dXK"], w_out, dwide, part)
+        wd_cin_fold(part, Gs[k - 1])
+        wd_cin_layer_backward(X, F, D, W, layers, k, bufs["XK"], bufs["dXK"], w_out, dwide, bufs["g0"], dX,
+                              perm=perm, blocks=blocks)
+    wd_cin_wout_partial(dwide, bufs["p"], bufs["part_o"])
+    wd_cin_fold(bufs["part_o"], g_out)
+    return dX
 
 
 # ----------------------------------------------------------------------------- held-out evaluation

@@ -12,6 +12,9 @@ num_iters (= --steps), alpha (LR). Extra: --fail_rank/--fail_step fault injectio
 every widedeep flag applies, the final JSON gains fm_term, SSP / ASP need --transport collective.
 --model dcn is widedeep with --cross_layers (default 3, 1..4) Deep & Cross layers over its whole input
 (WideDeepConfig(cross_layers=L)): every widedeep flag applies, the final JSON gains cross_layers, collective only.
+--model xdeepfm is widedeep with a Compressed Interaction Network over its field embeddings, --cin_layers H1,H2,...
+(default 64,64; 1..3 multiples of 16 in [16, 128]; WideDeepConfig(cin_layers=...)): every widedeep flag applies, the
+final JSON gains cin_layers, collective only.
 --model ffm is the field-aware FM (models/ffm.py): --ffm_k factors per partner field; the synthetic stream takes
 --fm_fields / --fm_card, an --input file --ffm_fields F [--ffm_field_bounds a,b,...] (a key's field is its key
 range); the final JSON gains ffm_fields and ffm_k, collective only.
@@ -71,7 +74,7 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
                                                              "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v", "als",
-                                                             "gmm", "twotower"])
+                                                             "gmm", "twotower", "xdeepfm"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -168,6 +171,8 @@ def parse(argv=None):
     ap.add_argument("--fm_k", type=int, default=16, help="fm: factors per feature (k % 4 == 0, 4 <= k <= 60)")
     ap.add_argument("--cross_layers", type=int, default=None,
                     help="dcn: cross layers over the assembled input, 1..4 (default 3)")
+    ap.add_argument("--cin_layers", default=None,
+                    help="xdeepfm: CIN feature maps per layer, H1,H2,... (default 64,64)")
     ap.add_argument("--fm_fields", type=int, default=0,
                     help="fm, synthetic data: fields per sample, one active feature each (0: 8 with --small, else 64)")
     ap.add_argument("--fm_card", type=int, default=0,
@@ -252,7 +257,7 @@ def parse(argv=None):
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     if args.wide_optimizer == "ftrl":
-        if args.model not in ("widedeep", "deepfm", "dcn", "fm", "ffm"):
+        if args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "fm", "ffm"):
             ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm, dcn, fm and ffm, not {args.model}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
@@ -269,7 +274,7 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "dlrm", "fm", "ffm", "gbdt",
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "dlrm", "fm", "ffm", "gbdt",
                                                   "twotower"):
         ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm, ffm, gbdt and "
                  f"twotower, not {args.model}")
@@ -546,7 +551,7 @@ def parse(argv=None):
     elif args.ffm_fields or args.ffm_field_bounds:
         ap.error(f"--ffm_fields / --ffm_field_bounds: --model ffm only, not {args.model}")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
-        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm", "dcn")
+        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm", "dcn", "xdeepfm")
                           and args.consistency in ("ssp", "asp") else "collective")
     if args.model == "deepfm" and args.transport == "onesided":
         ap.error("--model deepfm with SSP / ASP needs --transport collective (the FM term is not built for the "
@@ -561,6 +566,18 @@ def parse(argv=None):
         if args.transport == "onesided":
             ap.error("--model dcn with SSP / ASP needs --transport collective (the cross layers are not built for the "
                      "one-sided transport)")
+    if args.cin_layers is not None and args.model != "xdeepfm":
+        ap.error(f"--cin_layers: --model xdeepfm only, not {args.model}")
+    if args.model == "xdeepfm":
+        try:
+            args.cin_layers = [int(h) for h in (args.cin_layers or "64,64").split(",")]
+        except ValueError:
+            ap.error(f"--model xdeepfm: --cin_layers {args.cin_layers!r} must be integers H1,H2,...")
+        if not 1 <= len(args.cin_layers) <= 3 or any(h % 16 or not 16 <= h <= 128 for h in args.cin_layers):
+            ap.error(f"--model xdeepfm: --cin_layers {args.cin_layers} must be 1..3 multiples of 16 in [16, 128]")
+        if args.transport == "onesided":
+            ap.error("--model xdeepfm with SSP / ASP needs --transport collective (the cin_layers are not built for "
+                     "the one-sided transport)")
     if args.wide_optimizer == "ftrl" and args.transport == "onesided":
         ap.error("--wide_optimizer ftrl with SSP / ASP needs --transport collective (the one-sided owners apply the "
                  "row-wise Adagrad only)")
@@ -662,7 +679,7 @@ def build(args, comm):
     dev = comm.device
     r = comm.rank
     seed = args.seed * 1000 + r
-    if args.model in ("widedeep", "deepfm", "dcn"):  # deepfm / dcn: the same model with the FM term / cross layers
+    if args.model in ("widedeep", "deepfm", "dcn", "xdeepfm"):  # the same model with the FM term / cross / CIN layers
         from .data.synthetic import CriteoSynth
         from .models.widedeep import WideDeep, WideDeepConfig
 
@@ -675,6 +692,7 @@ def build(args, comm):
         cfg = WideDeepConfig(consistency=args.consistency, staleness=args.staleness, transport=args.transport,
                              max_batch=B, fm_term=args.model == "deepfm",
                              cross_layers=args.cross_layers if args.model == "dcn" else 0,
+                             cin_layers=tuple(args.cin_layers) if args.model == "xdeepfm" else (),
                              **({"cards": SMALL_CARDS} if args.small else {}), **wide)
         m = WideDeep(cfg, comm)
         return m, {0: m.emb, 1: m.dense}, (lambda: CriteoSynth(B, cards=cfg.cards, device=dev, seed=seed)), \
@@ -1488,6 +1506,8 @@ def main(argv=None):
         ftrl_final["fm_term"] = True
     if args.model == "dcn":
         ftrl_final["cross_layers"] = args.cross_layers
+    if args.model == "xdeepfm":
+        ftrl_final["cin_layers"] = list(args.cin_layers)
     if args.model == "ffm":
         ftrl_final.update(ffm_fields=model.cfg.num_fields, ffm_k=model.cfg.k)
     clip_final = {}
