@@ -40,6 +40,8 @@
   extension, same rule.
 * ``_cink``     -- xDeepFM's Compressed Interaction Network layers over the assembled Wide & Deep input
   (``ops.wd_cin_forward`` / ``wd_cin_backward``): an eighteenth small torch extension, same rule.
+* ``_aink``     -- AutoInt's multi-head field self-attention layers over the assembled Wide & Deep input
+  (``ops.wd_attn_forward`` / ``wd_attn_backward``): a nineteenth small torch extension, same rule.
 """
 from __future__ import annotations
 
@@ -165,6 +167,11 @@ def cink():
     return _load("_cink", "gfx950 HIP Compressed Interaction Network kernels")
 
 
+def aink():
+    """Return the HIP AutoInt field self-attention kernel module or raise a loud error."""
+    return _load("_aink", "gfx950 HIP AutoInt field self-attention kernels")
+
+
 def runtime():
     """Return the C++ runtime module or raise."""
     return _load("_runtime", "C++ PS runtime", torch_ext=False)
@@ -240,6 +247,10 @@ def kmk_available() -> bool:
 
 def cink_available() -> bool:
     return _available(cink)
+
+
+def aink_available() -> bool:
+    return _available(aink)
 
 
 def native_dir() -> str:

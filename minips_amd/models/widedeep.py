@@ -90,6 +90,15 @@ class WideDeepConfig:
     # w_out are the dense layout's entry "cin" behind W1 (and "cross"), trained by the dense Adam. Collective
     # transport only, 1 <= T <= 3, H_k % 16 == 0 in [16, 128], F <= 64, emb_dim % 8 == 0 in [8, 64]. (): Wide&Deep's.
     cin_layers: tuple = ()
+    # AutoInt (Song et al., 2019): attn_layers interacting layers of attn_heads-head self-attention (head size
+    # attn_dim) with a residual over the F field embeddings; the last layer's output enters the wide logit through
+    # w_out (ops.wd_attn_forward behind the CIN, ops.wd_attn_backward behind its backward; the rule:
+    # csrc/kernels/attnint.h). The parameters W^1 | ... | W^T | w_out are the dense layout's entry "attn" behind W1
+    # (and "cross", "cin"), trained by the dense Adam. Collective transport only, 1 <= attn_layers <= 3, attn_dim in
+    # (16, 32), attn_heads * attn_dim <= 64, F <= 32, emb_dim % 8 == 0 in [8, 64]. 0: Wide&Deep's.
+    attn_layers: int = 0
+    attn_heads: int = 2
+    attn_dim: int = 32
 
     def __post_init__(self):
         if self.transport == "auto":
@@ -130,6 +139,19 @@ class WideDeepConfig:
                 ops.wd_cin_check(self.F, self.emb_dim, self.cin_layers)
             except RuntimeError as e:
                 raise ValueError(f"cin_layers: {e}") from None
+
+        if self.attn_layers:
+            if "onesided" in (self.transport, self.dense_transport):
+                raise ValueError("attn_layers needs transport 'collective' (the interacting layers are not built for "
+                                 "the one-sided transport)")
+            try:
+                ops.wd_attn_check(self.F, self.emb_dim, self.attn_cfg)
+            except RuntimeError as e:
+                raise ValueError(f"attn_layers: {e}") from None
+
+    @property
+    def attn_cfg(self):
+        return (self.attn_layers, self.attn_heads, self.attn_dim)
 
     @property
     def F(self):
@@ -274,6 +296,11 @@ class WideDeep(LookaheadPlans):
                 n_cin = ops.wd_cin_layout(cfg.F, cfg.cin_layers)[1]
                 self.layout["cin"] = (off, (n_cin,))
                 off += n_cin
+            if i == 0 and cfg.attn_layers:
+                # AutoInt's W^1 | ... | W^T | w_out (ops.wd_attn_layout), behind "cin": layer 1's bucket again
+                n_attn = ops.wd_attn_layout(cfg.F, cfg.emb_dim, cfg.attn_cfg)[1]
+                self.layout["attn"] = (off, (n_attn,))
+                off += n_attn
             if i > 0:
                 self.layout[f"b{i + 1}"] = (off, (n_out,))
                 off += _align(n_out, 64)
@@ -310,6 +337,11 @@ class WideDeep(LookaheadPlans):
             Ws, w_out = ops.wd_cin_views(self.view(full, "cin"), F, self.cfg.cin_layers)
             for W in Ws:
                 ops.kaiming_uniform_(W[:, :, :F], W.shape[1] * F, g)
+            ops.kaiming_uniform_(w_out, w_out.numel(), g)
+        if self.cfg.attn_layers:  # drawn after every existing parameter: those keep their values; N(0, 1 / Din)
+            Ws, w_out = ops.wd_attn_views(self.view(full, "attn"), self.cfg.F, self.cfg.emb_dim, self.cfg.attn_cfg)
+            for W in Ws:
+                W.copy_(torch.randn(W.shape, generator=g) / W.shape[0] ** 0.5)
             ops.kaiming_uniform_(w_out, w_out.numel(), g)
         return full.to(dev)
 
@@ -355,6 +387,8 @@ class WideDeep(LookaheadPlans):
                 self._bufs[B].update(self._cross_buffers(B, part=True))
             if cfg.cin_layers:  # the feature maps, their gradients and the per-chunk partial weight gradients
                 self._bufs[B]["cin"] = ops.wd_cin_buffers(B, cfg.F, cfg.emb_dim, cfg.cin_layers, dev)
+            if cfg.attn_layers:  # every layer's output, its gradient and the per-chunk partial weight gradients
+                self._bufs[B]["attn"] = ops.wd_attn_buffers(B, cfg.F, cfg.emb_dim, cfg.attn_cfg, dev)
         return self._bufs[B]
 
     def _cross_buffers(self, B, part=False):
@@ -374,6 +408,11 @@ class WideDeep(LookaheadPlans):
         """wide += the CIN term over the assembled X (where the cross layers run: it reads the pulled values)."""
         cfg = self.cfg
         ops.wd_cin_forward(b["X"], cfg.F, cfg.emb_dim, self.view(P, "cin"), cfg.cin_layers, b["wide"], b["cin"])
+
+    def _attn_forward(self, b, P):
+        """wide += the AutoInt term over the assembled X (behind the CIN: it reads the pulled values)."""
+        cfg = self.cfg
+        ops.wd_attn_forward(b["X"], cfg.F, cfg.emb_dim, self.view(P, "attn"), cfg.attn_cfg, b["wide"], b["attn"])
 
     def _forward(self, b, P):
         ops.linear_fwd(b["X"], self.view(P, "W1"), None, "relu", out=b["H1"])
@@ -396,6 +435,8 @@ class WideDeep(LookaheadPlans):
             self._cross_forward(b, P)
         if self.cfg.cin_layers:
             self._cin_forward(b, P)
+        if self.cfg.attn_layers:
+            self._attn_forward(b, P)
         self._forward(b, P)
         h = self.cfg.hidden[-1]
         w4 = self.view(P, "w4").float()
@@ -418,6 +459,8 @@ class WideDeep(LookaheadPlans):
                 bufs[B].update(self._cross_buffers(B))
             if cfg.cin_layers:
                 bufs[B]["cin"] = ops.wd_cin_buffers(B, cfg.F, cfg.emb_dim, cfg.cin_layers, dev, train=False)
+            if cfg.attn_layers:
+                bufs[B]["attn"] = ops.wd_attn_buffers(B, cfg.F, cfg.emb_dim, cfg.attn_cfg, dev, train=False)
         return bufs[B]
 
     def evaluate(self, batches, evaluator=None) -> dict:
@@ -452,6 +495,8 @@ class WideDeep(LookaheadPlans):
                 self._cross_forward(b, P)
             if cfg.cin_layers:
                 self._cin_forward(b, P)
+            if cfg.attn_layers:
+                self._attn_forward(b, P)
             self._forward(b, P)
             ev.update_head(b["H3"], w4[:h], w4[h:h + 1], b["wide"], labels)
         ev.reduce(self.comm)
@@ -516,6 +561,8 @@ class WideDeep(LookaheadPlans):
             self._cross_forward(b, P)
         if cfg.cin_layers:  # xDeepFM: wide += <w_out, pooled CIN maps>; the pulled values again
             self._cin_forward(b, P)
+        if cfg.attn_layers:  # AutoInt: wide += <w_out, E^T>; the pulled values again
+            self._attn_forward(b, P)
         sink = self.dense.slab_sink() if hasattr(self.dense, "slab_sink") else None
         side = self._side
         defer = _HEAD_DEFER and side.stream is not None
@@ -556,7 +603,8 @@ class WideDeep(LookaheadPlans):
             ops.linear_dgrad(b["dH1"], self.view(P, "W1"), n_cols=F * D, out=b["dX"])
         # W's last reader of the step is issued: a side-stream dense Adam may start after this point
         adam_point = _ADAM_AFTER_DGRAD and self.comm.world == 1
-        w_read = side.point() if adam_point and not cfg.cross_layers and not cfg.cin_layers else None
+        w_read = (side.point() if adam_point and not cfg.cross_layers and not cfg.cin_layers and not cfg.attn_layers
+                  else None)
         if cfg.fm_term:  # DeepFM: dX += dz (S - v) per lookup, in the order the dgrad wrote the rows
             ops.wd_fm_backward(b["X"], b["S"], b["dwide"], b["dX"], F, D, perm=plan.csr[2] if sorted_rows else None)
         if cfg.cross_layers:
@@ -575,6 +623,13 @@ class WideDeep(LookaheadPlans):
             # the point the side-stream Adam waits for lies behind its last fold as well
             ops.wd_cin_backward(b["X"], F, D, self.view(P, "cin"), cfg.cin_layers, b["dwide"], b["dX"], b["cin"],
                                 self.view(G, "cin"), perm=plan.csr[2] if sorted_rows else None)
+            w_read = side.point() if adam_point else None
+        if cfg.attn_layers:
+            # AutoInt: per layer T .. 1 the backward (dE^{l-1} and the partial weight gradients, folded into G);
+            # layer 1 adds the embedding gradient to dX. It reads the pulled values and writes G like the CIN
+            # backward, so the point the side-stream Adam waits for lies behind its last fold as well
+            ops.wd_attn_backward(b["X"], F, D, self.view(P, "attn"), cfg.attn_cfg, b["dwide"], b["dX"], b["attn"],
+                                 self.view(G, "attn"), perm=plan.csr[2] if sorted_rows else None)
             w_read = side.point() if adam_point else None
         if _W1_LATE:  # the layer-1 weight gradient beside the memory-bound embedding backward instead
             with side.fork():

@@ -13,8 +13,8 @@ import math
 
 import torch
 
-from .._native import (alsk, cink, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, kmk, ldak,
-                       optk, w2vk, wdftrlk)
+from .._native import (aink, alsk, cink, dcnk, dfmk, evalk, ffmk, fmk, ftrlk, gbdtk, gmmfk, gmmk, ibsk, kernels, kmk,
+                       ldak, optk, w2vk, wdftrlk)
 
 EPI_STORE_F32 = 0
 EPI_ATOMIC_F32 = 1
@@ -1152,6 +1152,226 @@ def wd_cin_backward(X, F, D, Pc, layers, dwide, dX, bufs, Gc, perm=None, blocks=
                               perm=perm, blocks=blocks)
     wd_cin_wout_partial(dwide, bufs["p"], bufs["part_o"])
     wd_cin_fold(bufs["part_o"], g_out)
+    return dX
+
+
+# ----------------------------------------------------------------------------- AutoInt's interacting layers
+ATTN_MAX_T = 3        # csrc/kernels/attnint.h: kAttnMaxT, kAttnMaxM, kAttnMaxD, kAttnMaxA, kAttnChunk, kAttnMaxChunks
+ATTN_MAX_F = 32
+ATTN_MAX_D = 64
+ATTN_MAX_A = 64
+ATTN_CHUNK = 32
+ATTN_MAX_CHUNKS = 512
+
+
+def wd_attn_check(F, D, cfg):
+    """The shapes of csrc/kernels/attnint.h's rule (cfg = (T layers, H heads, head size d)), or a RuntimeError naming
+    what is outside it."""
+    cfg = tuple(cfg)
+    if len(cfg) != 3 or any(isinstance(v, bool) or not isinstance(v, int) for v in cfg):
+        raise RuntimeError(f"wd_attn: cfg is {cfg!r}, expected (layers, heads, head size) integers")
+    T, H, d = cfg
+    if not 1 <= T <= ATTN_MAX_T:
+        raise RuntimeError(f"wd_attn: {T} layers, expected 1 .. {ATTN_MAX_T}")
+    if d not in (16, 32) or H < 1 or H * d > ATTN_MAX_A:
+        raise RuntimeError(f"wd_attn: {H} heads of size {d}, expected a size in (16, 32) and heads * size <= "
+                           f"{ATTN_MAX_A}")
+    if not 1 <= F <= ATTN_MAX_F:
+        raise RuntimeError(f"wd_attn: F is {F}, expected 1 <= F <= {ATTN_MAX_F}")
+    if D % 8 or not 8 <= D <= ATTN_MAX_D:
+        raise RuntimeError(f"wd_attn: D is {D}, expected a multiple of 8 in [8, {ATTN_MAX_D}]")
+    return cfg
+
+
+def wd_attn_chunk(B):
+    """Samples per partial of the batch sums: a function of B alone (attnint.h's attn_chunk)."""
+    B = int(B)
+    return ATTN_CHUNK if B <= ATTN_CHUNK * ATTN_MAX_CHUNKS else (-(-B // ATTN_MAX_CHUNKS) + 3) // 4 * 4
+
+
+def wd_attn_nchunks(B):
+    return -(-int(B) // wd_attn_chunk(B))
+
+
+def wd_attn_layout(F, D, cfg):
+    """The flat parameter block W^1 | ... | W^T | w_out, each part 64-aligned: ([(offset, shape)] in that order,
+    total). W^l is [Din_l, 4 A] (columns Q | K | V | R) with Din_1 = D, Din_l = A = H d; w_out is [F A]."""
+    T, H, d = cfg
+    A, din, off, parts = H * d, D, 0, []
+    for _ in range(T):
+        parts.append((off, (din, 4 * A)))
+        off += (din * 4 * A + 63) // 64 * 64
+        din = A
+    parts.append((off, (F * A,)))
+    return parts, off + (F * A + 63) // 64 * 64
+
+
+def wd_attn_views(flat, F, D, cfg):
+    """([W^1 .. W^T], w_out) as views of a flat block laid out by wd_attn_layout."""
+    parts, _ = wd_attn_layout(F, D, cfg)
+    views = [flat[o: o + math.prod(s)].view(s) for o, s in parts]
+    return views[:-1], views[-1]
+
+
+def wd_attn_buffers(B, F, D, cfg, device, train=True):
+    """The buffers of a batch size: EK bf16 [B, T, F, A] (every layer's output); for training also dEK and the
+    per-chunk partials -- ``part`` is sized for the largest layer and reused layer by layer (each fold runs before
+    the next backward), so the workspace is at most ATTN_MAX_CHUNKS copies of the largest W^l."""
+    T, H, d = cfg
+    A = H * d
+    bufs = dict(EK=torch.zeros(B, T, F, A, dtype=torch.bfloat16, device=device))
+    if train:
+        nch = wd_attn_nchunks(B)
+        bufs.update(dEK=torch.zeros(B, T, F, A, dtype=torch.bfloat16, device=device),
+                    part=torch.empty(nch * max(D, A) * 4 * A, dtype=torch.float32, device=device),
+                    part_o=torch.empty(nch, F * A, dtype=torch.float32, device=device))
+    return bufs
+
+
+def _attn_bf(t):
+    return t.to(torch.bfloat16).float()
+
+
+def _attn_recompute(X, F, D, W, cfg, l, EK):
+    """(E^{l-1}, Q, K, V [B, H, m, d], R [B, m, A], P [B, H, m, m]) of layer l with the rule's roundings, fp32."""
+    T, H, d = cfg
+    A, B = H * d, X.shape[0]
+    E = X[:, : F * D].float().view(B, F, D) if l == 1 else EK[:, l - 2].float()
+    Y = E @ W.float()
+    Q, K, V = (_attn_bf(Y[..., i * A: (i + 1) * A]).view(B, F, H, d).transpose(1, 2) for i in range(3))
+    S = Q @ K.transpose(-1, -2)
+    p = torch.exp(S - S.max(-1, keepdim=True).values)
+    return E, Q, K, V, Y[..., 3 * A:], _attn_bf(p / p.sum(-1, keepdim=True))
+
+
+def _attn_shapes_ok(op, X, F, D, W, cfg, l, EK):
+    T, H, d = wd_attn_check(F, D, cfg)
+    din = D if l == 1 else H * d
+    if not 1 <= l <= T or tuple(W.shape) != (din, 4 * H * d) or tuple(EK.shape) != (X.shape[0], T, F, H * d):
+        raise RuntimeError(f"{op}: W {tuple(W.shape)} / EK {tuple(EK.shape)} do not fit layer {l} of {cfg}")
+
+
+def wd_attn_layer_forward(X, F, D, W, cfg, l, EK, blocks=0):
+    """One interacting layer of AutoInt (the rule: csrc/kernels/attnint.h): E^l = bf16(relu(softmax(Q K^T) V + R))
+    per head over the F rows of E^{l-1} (X's embedding columns for l = 1, EK[:, l - 2] above), written to
+    EK[:, l - 1]. One gfx950 MFMA launch on the GPU (Q, K, V, P exist only in registers); the CPU path is the fp32
+    reference of the rule."""
+    F, D, l, cfg = int(F), int(D), int(l), tuple(int(v) for v in cfg)
+    if _gpu(X):
+        aink().wd_attn_layer_forward(X, F, D, W, cfg[0], cfg[1], cfg[2], l, EK, int(blocks))
+        return EK
+    _attn_shapes_ok("wd_attn_layer_forward", X, F, D, W, cfg, l, EK)
+    _, _, _, V, R, P = _attn_recompute(X, F, D, W, cfg, l, EK)
+    O = (P @ V).transpose(1, 2).reshape(R.shape)
+    EK[:, l - 1] = torch.relu(O + R).to(torch.bfloat16)
+    return EK
+
+
+def wd_attn_output(EK, d, w_out, wide, blocks=0):
+    """wide[b] += <w_out, E^T_b> over the last layer's output (in place)."""
+    if _gpu(EK):
+        aink().wd_attn_output(EK, int(d), w_out, wide, int(blocks))
+        return wide
+    wide += EK[:, -1].float().reshape(EK.shape[0], -1) @ w_out.float()
+    return wide
+
+
+def wd_attn_layer_backward(X, F, D, W, cfg, l, EK, dEK, w_out, dwide, dX, part, perm=None, blocks=0):
+    """One layer of the AutoInt backward (csrc/kernels/attnint.h), recomputing Q, K, V, P from E^{l-1}: dE^{l-1} goes
+    to dEK[:, l - 2] (l > 1) or is added into dX through perm (l = 1; out-of-range perm entries are skipped), and
+    the per-chunk partials of dW^l are written to part fp32 [nchunks, Din_l, 4 A]. Call for l = T .. 1. In place."""
+    F, D, l, cfg = int(F), int(D), int(l), tuple(int(v) for v in cfg)
+    if _gpu(X):
+        aink().wd_attn_layer_backward(X, F, D, W, cfg[0], cfg[1], cfg[2], l, EK, dEK, w_out, dwide, perm, dX, part,
+                                      int(blocks))
+        return dX
+    _attn_shapes_ok("wd_attn_layer_backward", X, F, D, W, cfg, l, EK)
+    T, H, d = cfg
+    A, B = H * d, X.shape[0]
+    if dX.numel() != B * F * D or not dX.is_contiguous():
+        raise RuntimeError(f"wd_attn_layer_backward: dX {tuple(dX.shape)}, expected {B * F * D} contiguous elements")
+    if tuple(part.shape) != (wd_attn_nchunks(B), W.shape[0], 4 * A):
+        raise RuntimeError(f"wd_attn_layer_backward: part {tuple(part.shape)}, expected "
+                           f"{(wd_attn_nchunks(B), W.shape[0], 4 * A)}")
+    E, Q, K, V, _, P = _attn_recompute(X, F, D, W, cfg, l, EK)
+    dE = dEK[:, l - 1].float() if l < T else _attn_bf(dwide[:, None] * w_out.float()).view(B, F, A)
+    dY = torch.where(EK[:, l - 1].float() > 0, dE, torch.zeros_like(dE))
+    dYh = dY.view(B, F, H, d).transpose(1, 2)
+    dV = _attn_bf(P.transpose(-1, -2) @ dYh)
+    dP = dYh @ V.transpose(-1, -2)
+    dS = _attn_bf(P * (dP - (dP * P).sum(-1, keepdim=True)))
+    dQ, dK = _attn_bf(dS @ K), _attn_bf(dS.transpose(-1, -2) @ Q)
+    G = torch.cat([t.transpose(1, 2).reshape(B, F, A) for t in (dQ, dK, dV)] + [dY], -1)
+    ch = wd_attn_chunk(B)
+    for c in range(part.shape[0]):
+        s = slice(c * ch, (c + 1) * ch)
+        part[c] = torch.einsum("bik,bin->kn", E[s], G[s])
+    g = G @ W.float().t()
+    if l > 1:
+        dEK[:, l - 2] = g.to(torch.bfloat16)
+        return dX
+    n = B * F
+    dx, g = dX.view(n, D), g.reshape(n, D)
+    if perm is None:
+        dx.copy_((dx.float() + g).to(torch.bfloat16))
+    else:
+        r = perm.long()
+        ok = (r >= 0) & (r < n)
+        r = r[ok]
+        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
+    return dX
+
+
+def wd_attn_wout_partial(EK, d, dwide, part):
+    """part[chunk, o] = sum over the chunk's samples of dwide[b] E^T_b[o] (written)."""
+    if _gpu(EK):
+        aink().wd_attn_wout_partial(EK, int(d), dwide, part)
+        return part
+    ch, et = wd_attn_chunk(EK.shape[0]), EK[:, -1].float().reshape(EK.shape[0], -1)
+    for c in range(part.shape[0]):
+        part[c] = dwide[c * ch: (c + 1) * ch] @ et[c * ch: (c + 1) * ch]
+    return part
+
+
+def wd_attn_fold(part, G):
+    """G += the chunks of ``part`` added in chunk order (fp32; G has the shape of one chunk)."""
+    if _gpu(part):
+        aink().wd_attn_fold(part, G)
+        return G
+    s = torch.zeros_like(G)
+    for c in range(part.shape[0]):
+        s = s + part[c].view(G.shape)
+    G += s
+    return G
+
+
+def wd_attn_forward(X, F, D, Pc, cfg, wide, bufs, blocks=0):
+    """The AutoInt term over the assembled input: every interacting layer, then wide += <w_out, E^T>. Pc is the flat
+    bf16 parameter block (wd_attn_layout), bufs come from wd_attn_buffers."""
+    cfg = tuple(int(v) for v in cfg)
+    Ws, w_out = wd_attn_views(Pc, F, D, cfg)
+    for l in range(1, cfg[0] + 1):
+        wd_attn_layer_forward(X, F, D, Ws[l - 1], cfg, l, bufs["EK"], blocks)
+    wd_attn_output(bufs["EK"], cfg[2], w_out, wide, blocks)
+    return wide
+
+
+def wd_attn_backward(X, F, D, Pc, cfg, dwide, dX, bufs, Gc, perm=None, blocks=0):
+    """The AutoInt backward from dwide: for l = T .. 1 the layer's backward (dE^{l-1}, and the per-chunk partials of
+    dW^l, folded in chunk order and ADDED into the fp32 gradient block Gc laid out like Pc); the embedding gradient
+    is added to dX by layer 1; dw_out likewise from per-chunk partials."""
+    cfg = tuple(int(v) for v in cfg)
+    Ws, w_out = wd_attn_views(Pc, F, D, cfg)
+    Gs, g_out = wd_attn_views(Gc, F, D, cfg)
+    nch = wd_attn_nchunks(X.shape[0])
+    for l in range(cfg[0], 0, -1):
+        W = Ws[l - 1]
+        part = bufs["part"][: nch * W.numel()].view(nch, W.shape[0], W.shape[1])
+        wd_attn_layer_backward(X, F, D, W, cfg, l, bufs["EK"], bufs["dEK"], w_out, dwide, dX, part, perm=perm,
+                               blocks=blocks)
+        wd_attn_fold(part, Gs[l - 1])
+    wd_attn_wout_partial(bufs["EK"], cfg[2], dwide, bufs["part_o"])
+    wd_attn_fold(bufs["part_o"], g_out)
     return dX
 
 

@@ -15,6 +15,9 @@ every widedeep flag applies, the final JSON gains fm_term, SSP / ASP need --tran
 --model xdeepfm is widedeep with a Compressed Interaction Network over its field embeddings, --cin_layers H1,H2,...
 (default 64,64; 1..3 multiples of 16 in [16, 128]; WideDeepConfig(cin_layers=...)): every widedeep flag applies, the
 final JSON gains cin_layers, collective only.
+--model autoint is widedeep with AutoInt's interacting layers (multi-head self-attention with a residual over its field
+embeddings): --attn_layers (default 3, 1..3), --attn_heads (2), --attn_dim (head size, 32;
+WideDeepConfig(attn_layers=...)): every widedeep flag applies, the final JSON gains the three, collective only.
 --model ffm is the field-aware FM (models/ffm.py): --ffm_k factors per partner field; the synthetic stream takes
 --fm_fields / --fm_card, an --input file --ffm_fields F [--ffm_field_bounds a,b,...] (a key's field is its key
 range); the final JSON gains ffm_fields and ffm_k, collective only.
@@ -74,7 +77,7 @@ def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="widedeep", choices=["widedeep", "mlp", "dlrm", "gpt2", "lr", "kmeans", "fm",
                                                              "deepfm", "dcn", "ffm", "gbdt", "lda", "w2v", "als",
-                                                             "gmm", "twotower", "xdeepfm"])
+                                                             "gmm", "twotower", "xdeepfm", "autoint"])
     ap.add_argument("--steps", "--num_iters", dest="steps", type=int, default=20)
     ap.add_argument("--batch", "--batch_size", dest="batch", type=int, default=0)
     ap.add_argument("--consistency", "--kModelType", dest="consistency", default="bsp", type=str.lower)
@@ -173,6 +176,9 @@ def parse(argv=None):
                     help="dcn: cross layers over the assembled input, 1..4 (default 3)")
     ap.add_argument("--cin_layers", default=None,
                     help="xdeepfm: CIN feature maps per layer, H1,H2,... (default 64,64)")
+    ap.add_argument("--attn_layers", type=int, default=None, help="autoint: interacting layers, 1..3 (default 3)")
+    ap.add_argument("--attn_heads", type=int, default=None, help="autoint: heads per layer (default 2)")
+    ap.add_argument("--attn_dim", type=int, default=None, help="autoint: head size, 16 or 32 (default 32)")
     ap.add_argument("--fm_fields", type=int, default=0,
                     help="fm, synthetic data: fields per sample, one active feature each (0: 8 with --small, else 64)")
     ap.add_argument("--fm_card", type=int, default=0,
@@ -257,7 +263,7 @@ def parse(argv=None):
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--sparse_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
     if args.wide_optimizer == "ftrl":
-        if args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "fm", "ffm"):
+        if args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "autoint", "fm", "ffm"):
             ap.error(f"--wide_optimizer ftrl supports --model widedeep, deepfm, dcn, fm and ffm, not {args.model}")
         if not args.ftrl_alpha > 0 or not (args.ftrl_beta >= 0 and args.ftrl_l1 >= 0 and args.ftrl_l2 >= 0):
             ap.error("--wide_optimizer ftrl: --ftrl_alpha > 0, --ftrl_beta, --ftrl_l1 and --ftrl_l2 >= 0")
@@ -274,8 +280,8 @@ def parse(argv=None):
         ap.error("--lr_min_ratio needs --lr_decay_steps")
     if args.eval_every < 0 or (args.eval_every > 0 and args.eval_batches < 1):
         ap.error("--eval_every must be >= 0 and --eval_batches >= 1")
-    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "dlrm", "fm", "ffm", "gbdt",
-                                                  "twotower"):
+    if args.eval_every > 0 and args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "autoint", "dlrm", "fm",
+                                                  "ffm", "gbdt", "twotower"):
         ap.error(f"--eval_every: held-out evaluation supports --model widedeep, deepfm, dcn, dlrm, fm, ffm, gbdt and "
                  f"twotower, not {args.model}")
     gbdt_flags = [f"--{k}" for k in ("gbdt_depth", "gbdt_bins", "gbdt_lr", "gbdt_lambda", "gbdt_rows",
@@ -551,7 +557,7 @@ def parse(argv=None):
     elif args.ffm_fields or args.ffm_field_bounds:
         ap.error(f"--ffm_fields / --ffm_field_bounds: --model ffm only, not {args.model}")
     if args.transport == "auto":  # SSP / ASP run on the asynchronous one-sided PS (W&D, DLRM), BSP on collectives
-        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm", "dcn", "xdeepfm")
+        args.transport = ("onesided" if args.model in ("dlrm", "widedeep", "deepfm", "dcn", "xdeepfm", "autoint")
                           and args.consistency in ("ssp", "asp") else "collective")
     if args.model == "deepfm" and args.transport == "onesided":
         ap.error("--model deepfm with SSP / ASP needs --transport collective (the FM term is not built for the "
@@ -577,6 +583,20 @@ def parse(argv=None):
             ap.error(f"--model xdeepfm: --cin_layers {args.cin_layers} must be 1..3 multiples of 16 in [16, 128]")
         if args.transport == "onesided":
             ap.error("--model xdeepfm with SSP / ASP needs --transport collective (the cin_layers are not built for "
+                     "the one-sided transport)")
+    attn_flags = [n for n in ("attn_layers", "attn_heads", "attn_dim") if getattr(args, n) is not None]
+    if attn_flags and args.model != "autoint":
+        ap.error(f"--{attn_flags[0]}: --model autoint only, not {args.model}")
+    if args.model == "autoint":
+        args.attn_layers = 3 if args.attn_layers is None else args.attn_layers
+        args.attn_heads = 2 if args.attn_heads is None else args.attn_heads
+        args.attn_dim = 32 if args.attn_dim is None else args.attn_dim
+        if (not 1 <= args.attn_layers <= 3 or args.attn_dim not in (16, 32) or args.attn_heads < 1
+                or args.attn_heads * args.attn_dim > 64):
+            ap.error(f"--model autoint: --attn_layers {args.attn_layers} must be in [1, 3], --attn_dim {args.attn_dim} "
+                     f"16 or 32 and --attn_heads {args.attn_heads} * --attn_dim at most 64")
+        if args.transport == "onesided":
+            ap.error("--model autoint with SSP / ASP needs --transport collective (the attn_layers are not built for "
                      "the one-sided transport)")
     if args.wide_optimizer == "ftrl" and args.transport == "onesided":
         ap.error("--wide_optimizer ftrl with SSP / ASP needs --transport collective (the one-sided owners apply the "
@@ -679,7 +699,8 @@ def build(args, comm):
     dev = comm.device
     r = comm.rank
     seed = args.seed * 1000 + r
-    if args.model in ("widedeep", "deepfm", "dcn", "xdeepfm"):  # the same model with the FM term / cross / CIN layers
+    # deepfm / dcn / xdeepfm / autoint: the same model with the FM term / cross / CIN / attention layers
+    if args.model in ("widedeep", "deepfm", "dcn", "xdeepfm", "autoint"):
         from .data.synthetic import CriteoSynth
         from .models.widedeep import WideDeep, WideDeepConfig
 
@@ -693,6 +714,8 @@ def build(args, comm):
                              max_batch=B, fm_term=args.model == "deepfm",
                              cross_layers=args.cross_layers if args.model == "dcn" else 0,
                              cin_layers=tuple(args.cin_layers) if args.model == "xdeepfm" else (),
+                             **(dict(attn_layers=args.attn_layers, attn_heads=args.attn_heads, attn_dim=args.attn_dim)
+                                if args.model == "autoint" else {}),
                              **({"cards": SMALL_CARDS} if args.small else {}), **wide)
         m = WideDeep(cfg, comm)
         return m, {0: m.emb, 1: m.dense}, (lambda: CriteoSynth(B, cards=cfg.cards, device=dev, seed=seed)), \
@@ -1508,6 +1531,8 @@ def main(argv=None):
         ftrl_final["cross_layers"] = args.cross_layers
     if args.model == "xdeepfm":
         ftrl_final["cin_layers"] = list(args.cin_layers)
+    if args.model == "autoint":
+        ftrl_final.update(attn_layers=args.attn_layers, attn_heads=args.attn_heads, attn_dim=args.attn_dim)
     if args.model == "ffm":
         ftrl_final.update(ffm_fields=model.cfg.num_fields, ffm_k=model.cfg.k)
     clip_final = {}

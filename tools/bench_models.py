@@ -12,8 +12,9 @@ models: mlp (config 2, samples/s), gpt2 (config 4, tokens/s), dlrm (config 5, sa
         --wide_optimizer ftrl and reports wide_nnz), deepfm (widedeep with the FM term over its embeddings,
         WideDeepConfig(fm_term=True)), dcn (widedeep with --cross_layers Deep & Cross layers over its input,
         WideDeepConfig(cross_layers=L)), xdeepfm (widedeep with a --cin_layers Compressed Interaction Network over its
-        field embeddings, WideDeepConfig(cin_layers=...)), ffm (the field-aware FM, --ffm_fields x 262144 features,
-        --ffm_k),
+        field embeddings, WideDeepConfig(cin_layers=...)), autoint (widedeep with --attn_layers layers of
+        --attn_heads heads of size --attn_dim, WideDeepConfig(attn_layers=...)), ffm (the field-aware FM,
+        --ffm_fields x 262144 features, --ffm_k),
         gbdt (a boosting round of the fixed-point histogram GBDT over --batch resident samples per rank; --gbdt_depth,
         --gbdt_bins, --gbdt_features; ms_per_step is ms per tree), lda (a sweep of the fixed-point collapsed Gibbs
         sampler over --batch resident tokens per rank; --lda_topics; ms_per_step is ms per sweep), w2v (a clock of
@@ -285,12 +286,14 @@ def build(args, comm):
         return m, (lambda: m.train_step(torch.randn(B, cfg.dims, generator=g, device=dev))), B, "samples/s", \
             dict(model="mini-batch K-Means K=1000 D=128", seq_len=None,
                  **({"kmeans_step": "fused"} if args.kmeans_step == "fused" else {}))
-    if args.model in ("widedeep", "widedeep-ssp", "deepfm", "dcn", "xdeepfm"):
+    if args.model in ("widedeep", "widedeep-ssp", "deepfm", "dcn", "xdeepfm", "autoint"):
         from minips_amd.data.synthetic import CriteoSynth
         from minips_amd.models.widedeep import WideDeep, WideDeepConfig
 
         B = args.batch or 16384
-        bsp = args.model in ("widedeep", "deepfm", "dcn", "xdeepfm")
+        bsp = args.model in ("widedeep", "deepfm", "dcn", "xdeepfm", "autoint")
+        attn = (dict(attn_layers=args.attn_layers, attn_heads=args.attn_heads, attn_dim=args.attn_dim)
+                if args.model == "autoint" else {})
         fm_term = args.model == "deepfm"
         cross = args.cross_layers if args.model == "dcn" else 0
         cin = tuple(int(h) for h in args.cin_layers.split(",")) if args.model == "xdeepfm" else ()
@@ -301,7 +304,7 @@ def build(args, comm):
                         wide_grad_scale=args.ftrl_grad_scale or float(B * comm.world))
         cfg = WideDeepConfig(consistency="bsp" if bsp else "ssp", staleness=0 if bsp else max(1, args.staleness),
                              transport=args.transport, max_batch=B, fm_term=fm_term, cross_layers=cross,
-                             cin_layers=cin, **wide)
+                             cin_layers=cin, **attn, **wide)
         m = WideDeep(cfg, comm)
         if bsp:  # BSP, the look-ahead feeder below
             from minips_amd.models.feeder import LookaheadFeeder
@@ -320,9 +323,11 @@ def build(args, comm):
                 extra["cross_layers"] = cross
             if cin:
                 extra["cin_layers"] = list(cin)
+            extra.update(attn)
             name = ("DeepFM (Wide&Deep + FM term)" if fm_term else
                     f"DCN (Wide&Deep + {cross} cross layers)" if cross else
-                    f"xDeepFM (Wide&Deep + CIN {cin})" if cin else "Wide&Deep")
+                    f"xDeepFM (Wide&Deep + CIN {cin})" if cin else
+                    f"AutoInt (Wide&Deep + {tuple(attn.values())} attention)" if attn else "Wide&Deep")
             return m, feeder.step, B, "samples/s", dict(model=f"{name} Criteo BSP (collective)", seq_len=None,
                                                  consistency="bsp", transport=args.transport, feeder="lookahead",
                                                  **extra)
@@ -358,7 +363,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2", choices=["mlp", "gpt2", "dlrm", "dlrm-10b", "lr", "kmeans",
                                                          "widedeep-ssp", "widedeep", "fm", "deepfm", "dcn", "ffm",
-                                                         "gbdt", "lda", "w2v", "als", "gmm", "twotower", "xdeepfm"])
+                                                         "gbdt", "lda", "w2v", "als", "gmm", "twotower", "xdeepfm",
+                                                         "autoint"])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (samples or sequences)")
@@ -395,6 +401,9 @@ def main():
     ap.add_argument("--fm_k", "--fm-k", dest="fm_k", type=int, default=16, help="fm: factors per feature")
     ap.add_argument("--cross_layers", type=int, default=3, help="dcn: cross layers, 1..4")
     ap.add_argument("--cin_layers", default="64,64", help="xdeepfm: CIN feature maps per layer, H1,H2,...")
+    ap.add_argument("--attn_layers", type=int, default=3, help="autoint: interacting layers, 1..3")
+    ap.add_argument("--attn_heads", type=int, default=2, help="autoint: heads per layer")
+    ap.add_argument("--attn_dim", type=int, default=32, help="autoint: head size, 16 or 32")
     ap.add_argument("--ffm_k", "--ffm-k", dest="ffm_k", type=int, default=4, help="ffm: factors per partner field")
     ap.add_argument("--ffm_fields", "--ffm-fields", dest="ffm_fields", type=int, default=26, help="ffm: fields")
     ap.add_argument("--gbdt_depth", "--gbdt-depth", dest="gbdt_depth", type=int, default=6, help="gbdt: tree depth")
@@ -417,7 +426,8 @@ def main():
     args = ap.parse_args()
     if args.kmeans_step is not None and args.model != "kmeans":
         ap.error(f"--kmeans_step: --model kmeans only, not {args.model}")
-    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "fm", "ffm"):
+    if args.wide_optimizer == "ftrl" and args.model not in ("widedeep", "deepfm", "dcn", "xdeepfm", "autoint", "fm",
+                                                            "ffm"):
         ap.error("--wide_optimizer ftrl: --model widedeep, deepfm, dcn, fm and ffm only")
     if args.model == "dcn" and not 1 <= args.cross_layers <= 4:
         ap.error("--model dcn: --cross_layers must be in [1, 4]")
@@ -462,7 +472,7 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * el / args.steps, 3),
             "higher_is_better": True, "scaling": "weak",
             "dtype": ("bf16" if args.model in ("mlp", "gpt2", "dlrm", "dlrm-10b", "widedeep-ssp", "widedeep", "deepfm",
-                                                 "dcn", "xdeepfm")
+                                                 "dcn", "xdeepfm", "autoint")
                       else ("fp64" if args.value_dtype == "float64" and args.model == "lr" else "fp32")),
             "data": "synthetic", "last": float(out.float().sum()) if torch.is_tensor(out) else None,
             "config": dict(cfg, parallelism=f"ps-dp{comm.world}"),
