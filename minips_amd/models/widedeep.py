@@ -17,6 +17,7 @@ Step (every kernel is a gfx950 HIP kernel; comm is RCCL):
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 
 import torch
@@ -25,6 +26,7 @@ from .. import ops
 from ..ps.comm import Comm
 from ..utils import streams
 from ..utils.metrics import phase, traced
+from . import wd_terms
 from .layers import Replayer, SideStream
 from .feeder import LookaheadPlans
 
@@ -71,31 +73,20 @@ class WideDeepConfig:
     wide_l1: float = 0.0
     wide_l2: float = 0.0
     wide_grad_scale: float = 1.0
-    # DeepFM (Guo et al., 2017): the factorization-machine second-order term over the F field embeddings the
-    # deep tower reads, added to the wide logit (ops.wd_fm_forward after the assembly) and to the embedding
-    # gradient (ops.wd_fm_backward after the dX dgrad). No new parameter, table state or collective; the
-    # checkpoints are Wide&Deep's. Collective transport only, emb_dim in [1, 64].
+    # The interaction terms (models/wd_terms.py states each one's rule): all add to the wide logit, in this order, and
+    # to the embedding gradient; the parameterised ones are entries of the dense layout behind W1 ("cross", "cin",
+    # "attn"), trained by the dense Adam. Collective transport only. With all off (the default) the layout, the
+    # checkpoints and the step are Wide&Deep's.
+    # DeepFM's factorization-machine term over the field embeddings: no new parameter. emb_dim in [1, 64].
     fm_term: bool = False
-    # Deep & Cross (Wang et al., 2017): cross_layers = L > 0 vector-weight cross layers x_{l+1} = x_0 <x_l, w_l> + b_l
-    # + x_l over the whole assembled input (embeddings and dense features, d = F * emb_dim + n_dense columns), whose
-    # output enters the wide logit through one more vector w_c (ops.wd_cross_forward after the assembly and after the
-    # DeepFM term; ops.wd_cross_backward / wd_cross_fold after the dX dgrad). The (2L+1) align8(d) parameters are the
-    # dense layout's entry "cross" directly behind W1, trained by the dense Adam. Collective transport only,
-    # 1 <= L <= 4, emb_dim in [1, 64], d <= ops.CROSS_MAX_D. 0: the layout and the step are Wide&Deep's.
+    # Deep & Cross: L vector-weight cross layers over the whole assembled input (d = F * emb_dim + n_dense columns).
+    # 1 <= L <= 4, emb_dim in [1, 64], d <= ops.CROSS_MAX_D.
     cross_layers: int = 0
-    # xDeepFM (Lian et al., 2018): cin_layers = (H_1, ..., H_T) feature-map counts of a Compressed Interaction Network
-    # over the F field embeddings -- X^k[h] = sum_{i, j} W^k[h, i, j] (X^{k-1}[i] o X^0[j]), explicit vector-wise
-    # crosses of degree k + 1 -- whose sum-pooled maps enter the wide logit through w_out (ops.wd_cin_forward where the
-    # cross layers run, ops.wd_cin_backward behind them; the rule: csrc/kernels/cin.h). The parameters W^1 | ... | W^T |
-    # w_out are the dense layout's entry "cin" behind W1 (and "cross"), trained by the dense Adam. Collective
-    # transport only, 1 <= T <= 3, H_k % 16 == 0 in [16, 128], F <= 64, emb_dim % 8 == 0 in [8, 64]. (): Wide&Deep's.
+    # xDeepFM: (H_1, ..., H_T) feature-map counts of a Compressed Interaction Network over the field embeddings.
+    # 1 <= T <= 3, H_k % 16 == 0 in [16, 128], F <= 64, emb_dim % 8 == 0 in [8, 64].
     cin_layers: tuple = ()
-    # AutoInt (Song et al., 2019): attn_layers interacting layers of attn_heads-head self-attention (head size
-    # attn_dim) with a residual over the F field embeddings; the last layer's output enters the wide logit through
-    # w_out (ops.wd_attn_forward behind the CIN, ops.wd_attn_backward behind its backward; the rule:
-    # csrc/kernels/attnint.h). The parameters W^1 | ... | W^T | w_out are the dense layout's entry "attn" behind W1
-    # (and "cross", "cin"), trained by the dense Adam. Collective transport only, 1 <= attn_layers <= 3, attn_dim in
-    # (16, 32), attn_heads * attn_dim <= 64, F <= 32, emb_dim % 8 == 0 in [8, 64]. 0: Wide&Deep's.
+    # AutoInt: interacting layers of attn_heads-head self-attention (head size attn_dim) over the field embeddings.
+    # 1 <= attn_layers <= 3, attn_dim in (16, 32), attn_heads * attn_dim <= 64, F <= 32, emb_dim % 8 == 0 in [8, 64].
     attn_layers: int = 0
     attn_heads: int = 2
     attn_dim: int = 32
@@ -110,44 +101,17 @@ class WideDeepConfig:
         if self.wide_optimizer == "ftrl" and self.transport == "onesided":
             raise ValueError("wide_optimizer 'ftrl' needs transport 'collective' (the one-sided owners apply the "
                              "row-wise Adagrad only)")
-        if self.fm_term and "onesided" in (self.transport, self.dense_transport):
-            raise ValueError("fm_term needs transport 'collective' (the DeepFM term is not built for the one-sided "
-                             "transport)")
-        if self.fm_term and not 1 <= self.emb_dim <= 64:
-            raise ValueError(f"fm_term: emb_dim is {self.emb_dim}, expected 1 <= emb_dim <= 64")
         L = self.cross_layers
         if isinstance(L, bool) or not isinstance(L, int) or not 0 <= L <= ops.CROSS_MAX_L:
             raise ValueError(f"cross_layers is {L!r}, expected an int in [0, {ops.CROSS_MAX_L}]")
-        if L:
-            if "onesided" in (self.transport, self.dense_transport):
-                raise ValueError("cross_layers needs transport 'collective' (the cross layers are not built for the "
-                                 "one-sided transport)")
-            if not 1 <= self.emb_dim <= 64:
-                raise ValueError(f"cross_layers: emb_dim is {self.emb_dim}, expected 1 <= emb_dim <= 64")
-            d = self.F * self.emb_dim + self.n_dense
-            if d > ops.CROSS_MAX_D:
-                raise ValueError(f"cross_layers: the input has d = {d} columns, the kernels take d <= "
-                                 f"{ops.CROSS_MAX_D}")
         if not isinstance(self.cin_layers, (tuple, list)):
             raise ValueError(f"cin_layers is {self.cin_layers!r}, expected a tuple of feature-map counts")
         self.cin_layers = tuple(self.cin_layers)
-        if self.cin_layers:
+        for t in wd_terms.enabled(self):
             if "onesided" in (self.transport, self.dense_transport):
-                raise ValueError("cin_layers needs transport 'collective' (the CIN layers are not built for the "
-                                 "one-sided transport)")
-            try:
-                ops.wd_cin_check(self.F, self.emb_dim, self.cin_layers)
-            except RuntimeError as e:
-                raise ValueError(f"cin_layers: {e}") from None
-
-        if self.attn_layers:
-            if "onesided" in (self.transport, self.dense_transport):
-                raise ValueError("attn_layers needs transport 'collective' (the interacting layers are not built for "
-                                 "the one-sided transport)")
-            try:
-                ops.wd_attn_check(self.F, self.emb_dim, self.attn_cfg)
-            except RuntimeError as e:
-                raise ValueError(f"attn_layers: {e}") from None
+                raise ValueError(f"{t.option} needs transport 'collective' (the {t.what} not built for the one-sided "
+                                 "transport)")
+            t.check(self)
 
     @property
     def attn_cfg(self):
@@ -279,28 +243,19 @@ class WideDeep(LookaheadPlans):
         self.k_in = [cfg.F * cfg.emb_dim + cfg.n_dense, *cfg.hidden[:-1]]
         self.k_pad = [_align(self.k_in[0] + 1, _K1_ALIGN),
                       *self.k_in[1:]]
+        # the interaction terms that cfg switches on (wd_terms.TERMS' order: fm, cross, cin, attn), and the last of
+        # them that reads the pulled parameters (train_step's w_read rule)
+        self.terms = wd_terms.enabled(cfg)
+        self._last_reader = next((t for t in reversed(self.terms) if t.reads_params), None)
         self.layout = {}
         off = 0
         for i, n_out in enumerate(cfg.hidden):
             self.layout[f"W{i + 1}"] = (off, (n_out, self.k_pad[i]))
             off += _align(n_out * self.k_pad[i], 64)
-            if i == 0 and cfg.cross_layers:
-                # the cross parameters [w_0, b_0, ..., w_{L-1}, b_{L-1}, w_c] x align8(d), directly behind W1: inside
-                # layer 1's bucket, the last to go out -- _bucket_done(1, ...) releases the later buckets before the
-                # cross gradient (written after the dX dgrad) exists
-                self.layout["cross"] = (off, (2 * cfg.cross_layers + 1, _align(self.k_in[0])))
-                off += _align((2 * cfg.cross_layers + 1) * _align(self.k_in[0]), 64)
-            if i == 0 and cfg.cin_layers:
-                # the CIN parameters W^1 | ... | W^T | w_out (ops.wd_cin_layout, each part 64-aligned), behind W1 and
-                # "cross": inside layer 1's bucket for the same reason -- their gradient exists after the dX dgrad
-                n_cin = ops.wd_cin_layout(cfg.F, cfg.cin_layers)[1]
-                self.layout["cin"] = (off, (n_cin,))
-                off += n_cin
-            if i == 0 and cfg.attn_layers:
-                # AutoInt's W^1 | ... | W^T | w_out (ops.wd_attn_layout), behind "cin": layer 1's bucket again
-                n_attn = ops.wd_attn_layout(cfg.F, cfg.emb_dim, cfg.attn_cfg)[1]
-                self.layout["attn"] = (off, (n_attn,))
-                off += n_attn
+            for t in self.terms if i == 0 else ():  # the terms' parameters, directly behind W1 (wd_terms: name)
+                if t.name is not None:
+                    self.layout[t.name] = (off, t.shape(cfg, self.k_in[0]))
+                    off += _align(math.prod(self.layout[t.name][1]), 64)
             if i > 0:
                 self.layout[f"b{i + 1}"] = (off, (n_out,))
                 off += _align(n_out, 64)
@@ -329,20 +284,9 @@ class WideDeep(LookaheadPlans):
             w[:, self.k_in[i]:] = 0  # bias column and padding start at zero
         h = self.cfg.hidden[-1]
         ops.kaiming_uniform_(self.view(full, "w4")[:h], h, g)
-        if self.cfg.cross_layers:  # drawn after the existing parameters: those keep their values; b_l = 0
-            d = self.k_in[0]
-            ops.kaiming_uniform_(self.view(full, "cross")[0::2, :d], d, g)
-        if self.cfg.cin_layers:  # drawn last, the cross parameters included: every earlier value stays; the pad is 0
-            F = self.cfg.F
-            Ws, w_out = ops.wd_cin_views(self.view(full, "cin"), F, self.cfg.cin_layers)
-            for W in Ws:
-                ops.kaiming_uniform_(W[:, :, :F], W.shape[1] * F, g)
-            ops.kaiming_uniform_(w_out, w_out.numel(), g)
-        if self.cfg.attn_layers:  # drawn after every existing parameter: those keep their values; N(0, 1 / Din)
-            Ws, w_out = ops.wd_attn_views(self.view(full, "attn"), self.cfg.F, self.cfg.emb_dim, self.cfg.attn_cfg)
-            for W in Ws:
-                W.copy_(torch.randn(W.shape, generator=g) / W.shape[0] ** 0.5)
-            ops.kaiming_uniform_(w_out, w_out.numel(), g)
+        for t in self.terms:  # drawn after the existing parameters, term by term: every earlier value stays
+            if t.name is not None:
+                t.init(self, full, g)
         return full.to(dev)
 
     def view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
@@ -381,38 +325,17 @@ class WideDeep(LookaheadPlans):
                 dwide=torch.empty(B, dtype=torch.float32, device=dev),
                 loss=torch.zeros(1, dtype=torch.float32, device=dev),
             )
-            if cfg.fm_term:  # the per-sample column sums of the embeddings, kept for the backward
-                self._bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
-            if cfg.cross_layers:  # the cross layers' dot products and constants, and the partial batch sums
-                self._bufs[B].update(self._cross_buffers(B, part=True))
-            if cfg.cin_layers:  # the feature maps, their gradients and the per-chunk partial weight gradients
-                self._bufs[B]["cin"] = ops.wd_cin_buffers(B, cfg.F, cfg.emb_dim, cfg.cin_layers, dev)
-            if cfg.attn_layers:  # every layer's output, its gradient and the per-chunk partial weight gradients
-                self._bufs[B]["attn"] = ops.wd_attn_buffers(B, cfg.F, cfg.emb_dim, cfg.attn_cfg, dev)
+            for t in self.terms:
+                self._bufs[B].update(t.buffers(self, B, train=True))
         return self._bufs[B]
 
-    def _cross_buffers(self, B, part=False):
-        L, dev = self.cfg.cross_layers, self.comm.device
-        bufs = dict(p=torch.empty(B, L + 1, dtype=torch.float32, device=dev),
-                    k=torch.empty(L + 1, dtype=torch.float32, device=dev))
-        if part:
-            bufs["part"] = torch.empty(ops.wd_cross_part_shape(B, self.k_in[0], L), dtype=torch.float32, device=dev)
-        return bufs
-
-    def _cross_forward(self, b, P):
-        """wide += the cross layers' output over the assembled X (after the DeepFM term, before the head)."""
-        ops.wd_cross_forward(b["X"], self.k_in[0], self.view(P, "cross"), self.cfg.cross_layers, b["wide"], b["p"],
-                             b["k"])
-
-    def _cin_forward(self, b, P):
-        """wide += the CIN term over the assembled X (where the cross layers run: it reads the pulled values)."""
-        cfg = self.cfg
-        ops.wd_cin_forward(b["X"], cfg.F, cfg.emb_dim, self.view(P, "cin"), cfg.cin_layers, b["wide"], b["cin"])
-
-    def _attn_forward(self, b, P):
-        """wide += the AutoInt term over the assembled X (behind the CIN: it reads the pulled values)."""
-        cfg = self.cfg
-        ops.wd_attn_forward(b["X"], cfg.F, cfg.emb_dim, self.view(P, "attn"), cfg.attn_cfg, b["wide"], b["attn"])
+    def _terms_forward(self, b, P, early=None):
+        """wide += every enabled term over the assembled X, before the head reads it. train_step splits the chain:
+        ``early`` True runs only the terms that read no pulled parameter (before it waits for the previous step's
+        side-stream Adam; P is not needed), False only those that do (behind that wait)."""
+        for t in self.terms:
+            if early is None or early != t.reads_params:
+                t.forward(self, b, P)
 
     def _forward(self, b, P):
         ops.linear_fwd(b["X"], self.view(P, "W1"), None, "relu", out=b["H1"])
@@ -429,14 +352,7 @@ class WideDeep(LookaheadPlans):
         P = self.dense.get()
         F, D = self.cfg.F, self.cfg.emb_dim
         ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
-        if self.cfg.fm_term:
-            ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
-        if self.cfg.cross_layers:
-            self._cross_forward(b, P)
-        if self.cfg.cin_layers:
-            self._cin_forward(b, P)
-        if self.cfg.attn_layers:
-            self._attn_forward(b, P)
+        self._terms_forward(b, P)
         self._forward(b, P)
         h = self.cfg.hidden[-1]
         w4 = self.view(P, "w4").float()
@@ -453,14 +369,8 @@ class WideDeep(LookaheadPlans):
             X[:, self.k_in[0]] = 1.0
             bufs[B] = dict(X=X, wide=torch.empty(B, dtype=torch.float32, device=dev),
                            **{f"H{i + 1}": torch.empty(B, n, **bf) for i, n in enumerate(cfg.hidden)})
-            if cfg.fm_term:
-                bufs[B]["S"] = torch.empty(B, cfg.emb_dim, dtype=torch.float32, device=dev)
-            if cfg.cross_layers:
-                bufs[B].update(self._cross_buffers(B))
-            if cfg.cin_layers:
-                bufs[B]["cin"] = ops.wd_cin_buffers(B, cfg.F, cfg.emb_dim, cfg.cin_layers, dev, train=False)
-            if cfg.attn_layers:
-                bufs[B]["attn"] = ops.wd_attn_buffers(B, cfg.F, cfg.emb_dim, cfg.attn_cfg, dev, train=False)
+            for t in self.terms:
+                bufs[B].update(t.buffers(self, B, train=False))
         return bufs[B]
 
     def evaluate(self, batches, evaluator=None) -> dict:
@@ -489,14 +399,7 @@ class WideDeep(LookaheadPlans):
             b = self._eval_buffers(dense.shape[0])
             rows, plan = self.emb.get(keys, plan=self.emb.plan(keys))  # (not _take_plan: look-ahead plans survive)
             ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0])
-            if cfg.fm_term:
-                ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
-            if cfg.cross_layers:
-                self._cross_forward(b, P)
-            if cfg.cin_layers:
-                self._cin_forward(b, P)
-            if cfg.attn_layers:
-                self._attn_forward(b, P)
+            self._terms_forward(b, P)
             self._forward(b, P)
             ev.update_head(b["H3"], w4[:h], w4[h:h + 1], b["wide"], labels)
         ev.reduce(self.comm)
@@ -546,8 +449,7 @@ class WideDeep(LookaheadPlans):
         else:
             rows, plan = self.emb.get(keys, plan=plan)
             ops.wd_assemble(dense, rows, plan.inv, F, D, b["X"], b["wide"], ones_col=self.k_in[0], zero=b["loss"])
-        if cfg.fm_term:  # DeepFM: wide += the FM term of the embeddings just assembled (before the head reads it)
-            ops.wd_fm_forward(b["X"], F, D, b["wide"], b["S"])
+        self._terms_forward(b, None, early=True)
         if pend_side is not None:  # ... and its dense Adam ran (side stream) before the forward reads W
             streams.current(self.comm.device).wait_event(pend_side[1])
         ph.__exit__(None, None, None)
@@ -557,12 +459,7 @@ class WideDeep(LookaheadPlans):
         P = self.dense.get()
         scale = 1.0 / (B * self.comm.world)
         w4, gw4 = self.view(P, "w4"), self.view(G, "w4")
-        if cfg.cross_layers:  # DCN: wide += <x_L, w_c>; it reads the pulled values, so behind the Adam wait above
-            self._cross_forward(b, P)
-        if cfg.cin_layers:  # xDeepFM: wide += <w_out, pooled CIN maps>; the pulled values again
-            self._cin_forward(b, P)
-        if cfg.attn_layers:  # AutoInt: wide += <w_out, E^T>; the pulled values again
-            self._attn_forward(b, P)
+        self._terms_forward(b, P, early=False)  # these read the pulled values, so behind the Adam wait above
         sink = self.dense.slab_sink() if hasattr(self.dense, "slab_sink") else None
         side = self._side
         defer = _HEAD_DEFER and side.stream is not None
@@ -601,36 +498,18 @@ class WideDeep(LookaheadPlans):
                              perm=plan.csr[2], seg=D)
         else:
             ops.linear_dgrad(b["dH1"], self.view(P, "W1"), n_cols=F * D, out=b["dX"])
-        # W's last reader of the step is issued: a side-stream dense Adam may start after this point
+        # w_read: the point behind which the one-rank side-stream dense Adam may start. The Adam rewrites the pulled
+        # values P and clears G, so the point lies behind the compute stream's last launch that reads P or writes G: the
+        # dX dgrad when no term has reads_params, otherwise the backward of the last term that has it (its fold into G
+        # included). A term that touches neither (DeepFM's) may run behind the point. No point: the Adam forks behind
+        # everything issued on the compute stream
         adam_point = _ADAM_AFTER_DGRAD and self.comm.world == 1
-        w_read = (side.point() if adam_point and not cfg.cross_layers and not cfg.cin_layers and not cfg.attn_layers
-                  else None)
-        if cfg.fm_term:  # DeepFM: dX += dz (S - v) per lookup, in the order the dgrad wrote the rows
-            ops.wd_fm_backward(b["X"], b["S"], b["dwide"], b["dX"], F, D, perm=plan.csr[2] if sorted_rows else None)
-        if cfg.cross_layers:
-            # DCN: dX += sum_j m_j w_j per lookup, the per-chunk batch sums, then the cross gradients into G
-            Pc = self.view(P, "cross")
-            ops.wd_cross_backward(b["X"], self.k_in[0], b["p"], b["k"], b["dwide"], Pc, cfg.cross_layers, b["dX"], F, D,
-                                  b["part"], perm=plan.csr[2] if sorted_rows else None)
-            ops.wd_cross_fold(b["part"], Pc, self.k_in[0], cfg.cross_layers, self.view(G, "cross"))
-            # the side-stream Adam rewrites the pulled values and clears G: the cross backward still reads the
-            # former and the fold writes the latter, so here the point the Adam waits for lies behind the fold, not
-            # behind the dX dgrad (DeepFM's term touches neither and may stay behind the point)
-            w_read = side.point() if adam_point else None
-        if cfg.cin_layers:
-            # xDeepFM: per layer T .. 1 the weight gradient (partials, folded into G) and the data backward; layer 1
-            # adds the embedding gradient to dX. It reads the pulled values and writes G like the cross backward, so
-            # the point the side-stream Adam waits for lies behind its last fold as well
-            ops.wd_cin_backward(b["X"], F, D, self.view(P, "cin"), cfg.cin_layers, b["dwide"], b["dX"], b["cin"],
-                                self.view(G, "cin"), perm=plan.csr[2] if sorted_rows else None)
-            w_read = side.point() if adam_point else None
-        if cfg.attn_layers:
-            # AutoInt: per layer T .. 1 the backward (dE^{l-1} and the partial weight gradients, folded into G);
-            # layer 1 adds the embedding gradient to dX. It reads the pulled values and writes G like the CIN
-            # backward, so the point the side-stream Adam waits for lies behind its last fold as well
-            ops.wd_attn_backward(b["X"], F, D, self.view(P, "attn"), cfg.attn_cfg, b["dwide"], b["dX"], b["attn"],
-                                 self.view(G, "attn"), perm=plan.csr[2] if sorted_rows else None)
-            w_read = side.point() if adam_point else None
+        w_read = side.point() if adam_point and self._last_reader is None else None
+        perm = plan.csr[2] if sorted_rows else None  # the terms add to dX in the order the dgrad wrote its rows
+        for t in self.terms:
+            t.backward(self, b, P, G, perm)
+            if t is self._last_reader and adam_point:
+                w_read = side.point()
         if _W1_LATE:  # the layer-1 weight gradient beside the memory-bound embedding backward instead
             with side.fork():
                 _wgrad(b["dH1"], b["X"], self.view(G, "W1"), sink)

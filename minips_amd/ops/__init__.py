@@ -702,6 +702,37 @@ def wd_head_fold(B, Hd, dw, db, loss_sum, dH_colsum=None):
         (kernels() if _REC is None else _REC.lst).wd_head_fold(int(B), int(Hd), dw, db, loss_sum, dH_colsum)
 
 
+# ----------------------------------------------------------------------------- shared by the W&D terms' CPU references
+def _add_rows_perm(dX, g, perm, n, D):
+    """The terms' embedding gradient g (fp32, n * D elements, in lookup order) added into dX (bf16, n * D contiguous
+    elements) viewed as [n, D]: row perm[i] (i without ``perm``) becomes bf16(float(dX row) + g[i]); a ``perm`` entry
+    outside [0, n) is skipped. Returns dX."""
+    dx, g = dX.view(n, D), g.reshape(n, D)
+    if perm is None:
+        dx.copy_((dx.float() + g).to(torch.bfloat16))
+    else:
+        r = perm.long()
+        ok = (r >= 0) & (r < n)
+        r = r[ok]
+        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
+    return dX
+
+
+def _fold_chunks(part, G):
+    """G += the chunks of ``part`` added in chunk order (fp32; G has the shape of one chunk)."""
+    s = torch.zeros_like(G)
+    for c in range(part.shape[0]):
+        s = s + part[c].view(G.shape)
+    G += s
+    return G
+
+
+def _flat_views(flat, parts):
+    """([W^1 .. W^T], w_out) as views of a flat block laid out by ``parts`` = [(offset, shape)], w_out last."""
+    views = [flat[o: o + math.prod(s)].view(s) for o, s in parts]
+    return views[:-1], views[-1]
+
+
 # ----------------------------------------------------------------------------- DeepFM's interaction term
 def _wd_fm_check(X, F, D):
     if not 1 <= D <= 64 or F < 1:
@@ -745,17 +776,7 @@ def wd_fm_backward(X, S, dwide, dX, F, D, perm=None, blocks=0):
     if dX.numel() != n * D or not dX.is_contiguous():
         raise RuntimeError(f"wd_fm_backward: dX {tuple(dX.shape)}, expected {n * D} contiguous elements")
     v = X[:, : F * D].float().reshape(n, D)
-    dx = dX.view(n, D)
-    Sb = S.repeat_interleave(F, 0)
-    dz = dwide.repeat_interleave(F)[:, None]
-    if perm is None:
-        dx.copy_((dx.float() + dz * (Sb - v)).to(torch.bfloat16))
-        return dX
-    r = perm.long()
-    ok = (r >= 0) & (r < n)
-    r = r[ok]
-    dx[r] = (dx[r].float() + dz[ok] * (Sb[ok] - v[ok])).to(torch.bfloat16)
-    return dX
+    return _add_rows_perm(dX, dwide.repeat_interleave(F)[:, None] * (S.repeat_interleave(F, 0) - v), perm, n, D)
 
 
 # ----------------------------------------------------------------------------- Deep & Cross layers
@@ -862,15 +883,7 @@ def wd_cross_backward(X, d, p, k, dwide, Pc, L, dX, F, D, part, perm=None, block
     for j in range(1, L1):
         t = m[:, j: j + 1] * W[j, : F * D]
         g = g + t
-    g = g.reshape(n, D)
-    dx = dX.view(n, D)
-    if perm is None:
-        dx.copy_((dx.float() + g).to(torch.bfloat16))
-    else:
-        r = perm.long()
-        ok = (r >= 0) & (r < n)
-        r = r[ok]
-        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
+    _add_rows_perm(dX, g, perm, n, D)
     nch = part.shape[0]
     pad = nch * CROSS_CHUNK - B
     mc = torch.cat([m, m.new_zeros(pad, L1)]).view(nch, CROSS_CHUNK, L1)
@@ -966,9 +979,7 @@ def wd_cin_layout(F, layers):
 
 def wd_cin_views(flat, F, layers):
     """([W^1 .. W^T], w_out) as views of a flat block laid out by wd_cin_layout."""
-    parts, _ = wd_cin_layout(F, layers)
-    views = [flat[o: o + math.prod(s)].view(s) for o, s in parts]
-    return views[:-1], views[-1]
+    return _flat_views(flat, wd_cin_layout(F, layers)[0])
 
 
 def wd_cin_buffers(B, F, D, layers, device, train=True):
@@ -1068,16 +1079,7 @@ def wd_cin_layer_backward(X, F, D, W, layers, k, XK, dXK, w_out, dwide, g0, dX, 
     if k > 1:
         g0.copy_(g)
         return dX
-    n = B * F
-    dx, g = dX.view(n, D), g.reshape(n, D)
-    if perm is None:
-        dx.copy_((dx.float() + g).to(torch.bfloat16))
-    else:
-        r = perm.long()
-        ok = (r >= 0) & (r < n)
-        r = r[ok]
-        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
-    return dX
+    return _add_rows_perm(dX, g, perm, B * F, D)
 
 
 def wd_cin_layer_wgrad(X, F, D, layers, k, XK, dXK, w_out, dwide, part):
@@ -1117,11 +1119,7 @@ def wd_cin_fold(part, G):
     if _gpu(part):
         cink().wd_cin_fold(part, G)
         return G
-    s = torch.zeros_like(G)
-    for c in range(part.shape[0]):
-        s = s + part[c].view(G.shape)
-    G += s
-    return G
+    return _fold_chunks(part, G)
 
 
 def wd_cin_forward(X, F, D, Pc, layers, wide, bufs, blocks=0):
@@ -1208,9 +1206,7 @@ def wd_attn_layout(F, D, cfg):
 
 def wd_attn_views(flat, F, D, cfg):
     """([W^1 .. W^T], w_out) as views of a flat block laid out by wd_attn_layout."""
-    parts, _ = wd_attn_layout(F, D, cfg)
-    views = [flat[o: o + math.prod(s)].view(s) for o, s in parts]
-    return views[:-1], views[-1]
+    return _flat_views(flat, wd_attn_layout(F, D, cfg)[0])
 
 
 def wd_attn_buffers(B, F, D, cfg, device, train=True):
@@ -1310,16 +1306,7 @@ def wd_attn_layer_backward(X, F, D, W, cfg, l, EK, dEK, w_out, dwide, dX, part, 
     if l > 1:
         dEK[:, l - 2] = g.to(torch.bfloat16)
         return dX
-    n = B * F
-    dx, g = dX.view(n, D), g.reshape(n, D)
-    if perm is None:
-        dx.copy_((dx.float() + g).to(torch.bfloat16))
-    else:
-        r = perm.long()
-        ok = (r >= 0) & (r < n)
-        r = r[ok]
-        dx[r] = (dx[r].float() + g[ok]).to(torch.bfloat16)
-    return dX
+    return _add_rows_perm(dX, g, perm, B * F, D)
 
 
 def wd_attn_wout_partial(EK, d, dwide, part):
@@ -1338,11 +1325,7 @@ def wd_attn_fold(part, G):
     if _gpu(part):
         aink().wd_attn_fold(part, G)
         return G
-    s = torch.zeros_like(G)
-    for c in range(part.shape[0]):
-        s = s + part[c].view(G.shape)
-    G += s
-    return G
+    return _fold_chunks(part, G)
 
 
 def wd_attn_forward(X, F, D, Pc, cfg, wide, bufs, blocks=0):
